@@ -8,11 +8,14 @@ cap 10 Gauss-Newton iterations), inputs resident in HBM when the timed region st
 N GPUs = N processes (torch.distributed / RCCL only for the barrier + max-over-ranks timing;
 the path itself needs no collective: independent pairs, weak scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs
+is given and prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step, ...). With --full the
+line also carries
   roofline     — algorithmic bytes (833,392 B per alignment) / kernel time
                  (HIP events on the launch stream) against 8 TB/s HBM
   cpu_baseline — the CPU oracle (line-faithful restatement of the reference) timed on this
-                 box's host cores on the same pairs, plus the pose delta GPU vs CPU.
+                 box's host cores on the same pairs, plus the pose delta GPU vs CPU,
+and the secondary entries (other shapes and kernels) precede it.
 """
 from __future__ import annotations
 
@@ -361,6 +364,30 @@ def aggregate_rank_checks(rank_checks):
           "tolerance": "1e-4 rad / 1e-4 m (north_star)"}
     ok = bool(mr <= 1e-4 and mm <= 1e-4 and pd["n_tracked_equal"] and pd["ranks_checked"] == len(rank_checks))
     return pd, ok
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, d, rank=0, world=1, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the last timed step returned to its caller (dsdtm_sparse_align_batch_device: every pair's pose,
+    tracked count and per-level statistics) as <path>/<name>.npy in float64; ranks > 0 add _rank<r> to the names. Over
+    `limit` bytes in all (split evenly over the ranks), a fixed seeded sample of pairs is written, their indices in pair_index."""
+    from dsdtm_amd import capi
+    stats = np.frombuffer(d["stats"].cpu().numpy().tobytes(), dtype=capi.STATS_DTYPE)
+    arrays = {"T_cur_w": d["T_cur_w"].cpu().numpy().reshape(-1, 3, 4), "n_tracked": d["n_tracked"].cpu().numpy()}
+    arrays.update({"stats_" + k: stats[k] for k in capi.STATS_DTYPE.names})
+    n = len(arrays["n_tracked"])
+    per_pair = sum(a[0].size for a in arrays.values()) * 8
+    budget = limit // world - 4096                              # - the .npy headers
+    if n * per_pair > budget:
+        idx = np.sort(np.random.default_rng(0).choice(n, budget // (per_pair + 8), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["pair_index"] = idx
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + sfx + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def hip_event_ms(torch, stream, fn, launches):
@@ -921,15 +948,24 @@ def main():
                     help="untimed launches of the same step BEFORE the W warm-up steps, reported in the line as 'preroll': the GPU "
                          "comes out of idle over ~40 ms of load (tools/warmup_sweep.sh: the same 20 timed steps run 7 %% faster "
                          "behind 200 launches than behind 5); 0 = none")
-    ap.add_argument("--cpu-sample", type=int, default=1024, help="pairs timed on the CPU oracle (rank 0, N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline: value_from_idle, the roofline and fp64 blocks (with the one-stream "
+                         "burst they time), the CPU baselines and the parity of the last step against the CPU oracle (every rank's "
+                         "own when N > 1), the secondary entries; --no-cpu / --no-secondary leave parts out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (pose, tracked count, per-level statistics of every pair) as "
+                         "DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-sample", type=int, default=1024, help="--full: pairs timed on the CPU oracle (rank 0, N=1)")
     ap.add_argument("--rank-check-pairs", type=int, default=32,
-                    help="N > 1: pairs of its OWN last step every rank checks against the CPU oracle after the timed region "
+                    help="--full, N > 1: pairs of its OWN last step every rank checks against the CPU oracle after the timed region "
                          "(gathered into pose_delta_vs_cpu.ranks_checked; a rank over 1e-4 rad / m nulls value, exit 1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary roofline entries (other shapes, pyrDown)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines and the parity leg")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary roofline entries (other shapes, pyrDown)")
     ap.add_argument("--stub", action="store_true",
                     help="plumbing test without a GPU (tests/test_multiproc_cpu.py): gloo, no kernels, value null")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -1082,9 +1118,9 @@ def main():
         return el, ([x.elapsed_time(y) for x, y in ev] if per_kernel else None), (None if per_kernel else span[0].elapsed_time(span[1]))
 
     # For the record, the same W + K steps BEFORE the pre-roll, i.e. on a GPU that sat idle while the host prepared the
-    # batch and through streams in their first use: 'value_from_idle' in the line (what --preroll 0 reports as the value)
+    # batch and through streams in their first use: 'value_from_idle' in the line of --full (what --preroll 0 reports as the value)
     elapsed_idle = None
-    if args.preroll > 0:
+    if args.full and args.preroll > 0:
         elapsed_idle = timed_region()[0]
         d["T_steps"].copy_(d["T_seed"].unsqueeze(0).expand(n_slots, -1, -1))
         torch.cuda.synchronize()
@@ -1118,50 +1154,53 @@ def main():
         per_rank = shard.gather_over_ranks(per_rank[0], dist, dev if dist.get_backend() == "nccl" else torch.device("cpu"))
     ctx.check(ctx.lib.dsdtm_sparse_align_check(ctx.handle, stream.cuda_stream))   # no hand-over wait timed out in any launch
     d["T_cur_w"] = d["T_steps"][n_slots - 1].clone()  # the last step's results are the ones checked below
-    if per_kernel:
-        k_avg, k_min, k_extra = float(np.mean(kernel_ms)), float(np.min(kernel_ms)), {}
-        k_basis = "HIP events around every launch on the launch stream (one stream: launches do not overlap)"
-    else:
-        k_avg = span_ms / args.steps
-        k_min = None
-        # a short one-stream burst OUTSIDE the timed region: the duration of the kernel when nothing overlaps it
-        solo_n = 30
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(solo_n)]
-        torch.cuda.synchronize()
-        with torch.cuda.stream(streams[0]):
-            for k in range(solo_n):
-                d["T_steps"][k % n_slots].copy_(d["T_seed"], non_blocking=True)      # re-seed (outside the event pair, same stream)
-                evs[k][0].record(streams[0])
-                ctx.check(ctx.lib.dsdtm_sparse_align_batch_device(ctx.handle, C.byref(descs[k % n_slots]), C.byref(cam_struct), C.byref(prm),
-                                                                  streams[0].cuda_stream))
-                evs[k][1].record(streams[0])
-        streams[0].synchronize()
-        k_solo = float(np.mean([a.elapsed_time(b) for a, b in evs][5:]))
-        ov = pmc_summary().get("overlap", {})     # from the committed kernel trace of this binary (tools/profile.sh, case main)
-        k_extra = {"span_ms_per_step": k_avg,
-                   "kernel_ms_own_in_flight": ov.get("own_duration_avg_ns", 0) * 1e-6 or None,
-                   "launches_in_flight": ov.get("launches_in_flight_avg"),
-                   "in_flight_note": "a launch's own begin-to-end time and the number of launches in flight with the default streams: "
-                                     "rocprofv3 --kernel-trace of this command, committed in " + PMC_SUMMARY + " (null when that "
-                                     "summary was taken with another build of the library)",
-                   "kernel_ms_solo": k_solo,
-                   "kernel_ms_solo_note": f"mean of {solo_n - 5} launches on ONE stream after the timed region (HIP events around each): "
-                                          "the kernel's duration as rocprofv3 --kernel-trace reports it for a one-stream run"}
-        k_basis = (f"kernel_ms_avg = kernel_ms_solo: the kernel alone on one stream (HIP events around each launch of a burst right after "
-                   f"the timed region) — the duration rocprofv3 --kernel-trace reports and profiles/ holds; frac is computed from it. The timed "
-                   f"region issues its steps on {n_streams} streams (consecutive launches overlap at their edges): span_ms_per_step and "
-                   f"frac_overlapped describe that delivered rate")
-        k_extra["frac_overlapped"] = args.pairs * algorithmic_bytes(args.width, args.height, args.levels, args.patches) / (k_avg * 1e-3) / 1e9 / HBM_PEAK_GBS
-        k_extra["frac_overlapped_note"] = ("algorithmic bytes / span per step of the timed region: what the GPU delivers with ~3 launches in flight; "
-                                           "no single kernel's duration reproduces it (a launch's own begin-to-end time is kernel_ms_own_in_flight)")
-        k_span = k_avg
-        k_avg = k_solo
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d, rank, world)
+    if args.full:                                     # the kernel time behind the roofline block
+        if per_kernel:
+            k_avg, k_min, k_extra = float(np.mean(kernel_ms)), float(np.min(kernel_ms)), {}
+            k_basis = "HIP events around every launch on the launch stream (one stream: launches do not overlap)"
+        else:
+            k_avg = span_ms / args.steps
+            k_min = None
+            # a short one-stream burst OUTSIDE the timed region: the duration of the kernel when nothing overlaps it
+            solo_n = 30
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(solo_n)]
+            torch.cuda.synchronize()
+            with torch.cuda.stream(streams[0]):
+                for k in range(solo_n):
+                    d["T_steps"][k % n_slots].copy_(d["T_seed"], non_blocking=True)      # re-seed (outside the event pair, same stream)
+                    evs[k][0].record(streams[0])
+                    ctx.check(ctx.lib.dsdtm_sparse_align_batch_device(ctx.handle, C.byref(descs[k % n_slots]), C.byref(cam_struct), C.byref(prm),
+                                                                      streams[0].cuda_stream))
+                    evs[k][1].record(streams[0])
+            streams[0].synchronize()
+            k_solo = float(np.mean([a.elapsed_time(b) for a, b in evs][5:]))
+            ov = pmc_summary().get("overlap", {})     # from the committed kernel trace of this binary (tools/profile.sh, case main)
+            k_extra = {"span_ms_per_step": k_avg,
+                       "kernel_ms_own_in_flight": ov.get("own_duration_avg_ns", 0) * 1e-6 or None,
+                       "launches_in_flight": ov.get("launches_in_flight_avg"),
+                       "in_flight_note": "a launch's own begin-to-end time and the number of launches in flight with the default streams: "
+                                         "rocprofv3 --kernel-trace of this command, committed in " + PMC_SUMMARY + " (null when that "
+                                         "summary was taken with another build of the library)",
+                       "kernel_ms_solo": k_solo,
+                       "kernel_ms_solo_note": f"mean of {solo_n - 5} launches on ONE stream after the timed region (HIP events around each): "
+                                              "the kernel's duration as rocprofv3 --kernel-trace reports it for a one-stream run"}
+            k_basis = (f"kernel_ms_avg = kernel_ms_solo: the kernel alone on one stream (HIP events around each launch of a burst right after "
+                       f"the timed region) — the duration rocprofv3 --kernel-trace reports and profiles/ holds; frac is computed from it. The timed "
+                       f"region issues its steps on {n_streams} streams (consecutive launches overlap at their edges): span_ms_per_step and "
+                       f"frac_overlapped describe that delivered rate")
+            k_extra["frac_overlapped"] = args.pairs * algorithmic_bytes(args.width, args.height, args.levels, args.patches) / (k_avg * 1e-3) / 1e9 / HBM_PEAK_GBS
+            k_extra["frac_overlapped_note"] = ("algorithmic bytes / span per step of the timed region: what the GPU delivers with ~3 launches in flight; "
+                                               "no single kernel's duration reproduces it (a launch's own begin-to-end time is kernel_ms_own_in_flight)")
+            k_span = k_avg
+            k_avg = k_solo
 
     # N > 1: EVERY rank holds its own last step against the CPU oracle (the checker runs after the timed region, on that rank's
     # share of the host threads), and the verdicts are gathered: an N-GPU rate is only a result if ranks 1..N-1 aligned their
     # pairs too. (N = 1: rank 0 checks all its pairs below, in the cpu_baseline leg.)
     rank_checks = None
-    if world > 1 and args.rank_check_pairs > 0:
+    if args.full and world > 1 and args.rank_check_pairs > 0:
         n_chk = max(1, min(args.rank_check_pairs, args.pairs))
         if rank == 0:                         # the checker's library is (re)built by ONE rank if it is stale, never by all of them at once
             from tests import oracle_lib
@@ -1174,12 +1213,6 @@ def main():
     if rank == 0:
         n_total = args.pairs * world * args.steps
         value = n_total / elapsed
-        b_alg = algorithmic_bytes(args.width, args.height, args.levels, args.patches)
-        stats = np.frombuffer(d["stats"].cpu().numpy().tobytes(), dtype=capi.STATS_DTYPE)
-        iters = stats["iters"][:, :args.levels]
-        Tg = d["T_cur_w"].cpu().numpy()
-        ntg = d["n_tracked"].cpu().numpy()
-        err = np.array([synth.pose_error(Tg[i], d["T_true"][i]) for i in range(args.pairs)])
         out = {
             "metric": "frame-pair alignments/sec (640x480, 4 lvls, ~300 patches, 10 GN iters); pose delta vs CPU",
             "value": value, "unit": "alignments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1195,22 +1228,30 @@ def main():
             "per_rank_value": [r[1] / r[0] for r in per_rank],
             "ranks_seen": dist.get_world_size() if use_dist else 1,
             **({"barrier_backend": dist.get_backend()} if use_dist else {}),
-            "roofline": roofline_block("sparse_align_reg_kernel", args.pairs * b_alg, k_avg, k_min, args.pairs, b_alg, "alignment",
-                                       {"kernel_time_basis": k_basis, **k_extra}),
-            "fp64": fp64_block(args, k_avg),
-            "executed_iterations_per_level_mean": [float(x) for x in iters.mean(axis=0)],
-            "executed_iterations_total_mean": float(iters.sum(axis=1).mean()),
-            "n_tracked_mean": float(ntg.mean()),
-            "err_vs_ground_truth_median": {"rad": float(np.median(err[:, 0])), "m": float(np.median(err[:, 1]))},
             "library": ctx.lib.dsdtm_version().decode(), "library_sha": library_sha(),
-            "value_from_idle": (n_total / elapsed_idle) if elapsed_idle else None,
             "preroll": {"launches": args.preroll, "ms": preroll_ms,
                         "note": "untimed launches of the same step before the 'warmup' steps, on pose buffers of their own: the GPU "
                                 "leaves its idle clocks over ~40 ms of load (tools/warmup_sweep.sh, profiles/r03_warmup_sweep.txt); "
-                                "value_from_idle = the same W + K steps timed before the pre-roll, in this process; "
+                                "value_from_idle (--full) = the same W + K steps timed before the pre-roll, in this process; "
                                 "--preroll 0 makes that the value"},
         }
-        if not args.no_cpu and world == 1:
+        if args.full:
+            b_alg = algorithmic_bytes(args.width, args.height, args.levels, args.patches)
+            stats = np.frombuffer(d["stats"].cpu().numpy().tobytes(), dtype=capi.STATS_DTYPE)
+            iters = stats["iters"][:, :args.levels]
+            Tg = d["T_cur_w"].cpu().numpy()
+            ntg = d["n_tracked"].cpu().numpy()
+            err = np.array([synth.pose_error(Tg[i], d["T_true"][i]) for i in range(args.pairs)])
+            out.update({
+                "roofline": roofline_block("sparse_align_reg_kernel", args.pairs * b_alg, k_avg, k_min, args.pairs, b_alg, "alignment",
+                                           {"kernel_time_basis": k_basis, **k_extra}),
+                "fp64": fp64_block(args, k_avg),
+                "executed_iterations_per_level_mean": [float(x) for x in iters.mean(axis=0)],
+                "executed_iterations_total_mean": float(iters.sum(axis=1).mean()),
+                "n_tracked_mean": float(ntg.mean()),
+                "err_vs_ground_truth_median": {"rad": float(np.median(err[:, 0])), "m": float(np.median(err[:, 1]))},
+                "value_from_idle": (n_total / elapsed_idle) if elapsed_idle else None})
+        if args.full and not args.no_cpu and world == 1:
             sample = min(args.cpu_sample, args.pairs)
             rows, To, nto, sto = cpu_baselines(d, cam_struct, prm, sample)
             out.update(rows)
@@ -1232,7 +1273,7 @@ def main():
                 out["value"] = None
                 out["parity_failed"] = True
                 rc = 1
-        if rc == 0 and world == 1 and not args.no_secondary:
+        if args.full and rc == 0 and world == 1 and not args.no_secondary:
             try:
                 out["secondary"] = secondary_entries(torch, dev, ctx, cam_struct, stream, args)
             except Exception as e:          # the headline was measured and checked before this: it is printed whatever happens

@@ -9,7 +9,10 @@ oracle/_ref/libfast_ref.so, and this script runs that library (through oracle/fa
     Thirdparty/fast/test/test.cpp:16-54) — decoded here with zlib, no image library needed;
   * small synthetic images (noise, low contrast, a texture; one narrower than 22 columns, which takes
     the plain detector, faster_corner_10_sse.cpp:190-193).
-The fixture holds data only: pixel arrays and (x, y, score, is_nonmax) rows. Needs /root/reference:
+It also writes tests/golden/fast_reference_cases.npz: the same library's answers at barriers 20 / 5 / 75 on the
+cases of tests/test_detector_cpu.py::test_oracle_fast_matches_a_live_build_of_the_reference_sources (random and
+saturated images, odd sizes, one row-strided view at an odd base), so that test holds without the reference.
+The fixtures hold data only: pixel arrays and (x, y, score, is_nonmax) rows. Needs the reference's sources (make -C oracle ref):
 
     python tests/golden/make_golden_fast.py
 """
@@ -24,6 +27,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from dsdtm_amd import synth  # noqa: E402
 from tests import oracle_lib  # noqa: E402
+
+
+STRIDED_CASE = 7
+BARRIERS = (20, 5, 75)
 
 
 def read_png_gray8(path):
@@ -81,6 +88,27 @@ def main():
         d[k] = img; d[k + "_b20"] = oracle_lib.fast10_list_reference(img, 20)
     np.savez_compressed(os.path.join(HERE, "fast_reference.npz"), **d)
     print({k: v.shape for k, v in d.items()})
+    cases_fixture()
+
+
+def cases_fixture():
+    """tests/golden/fast_reference_cases.npz (see above)."""
+    assert oracle_lib.fast_ref_lib() is not None, "needs the reference's Thirdparty/fast build (make -C oracle ref)"
+    rng = np.random.default_rng(42)
+    cases = [rng.integers(0, 256, s, dtype=np.uint8) for s in [(50, 70), (33, 22), (7, 30), (90, 131), (6, 40)]]
+    cases += [(100 + rng.integers(-40, 41, (64, 64))).astype(np.uint8)]
+    cases += [np.clip(np.rint(synth.make_texture(96, 128, 3)), 0, 255).astype(np.uint8)]
+    cases += [rng.integers(0, 256, (80, 200), dtype=np.uint8)]                   # the test takes [:, 3:163]: stride != width, odd base
+    sat = rng.integers(0, 256, (40, 48), dtype=np.uint8); sat[sat < 30] = 0; sat[sat > 225] = 255   # saturating barriers
+    cases.append(sat)
+    c = {}
+    for i, img in enumerate(cases):
+        c[f"case{i}"] = img
+        view = img[:, 3:163] if i == STRIDED_CASE else img
+        for barrier in BARRIERS:
+            c[f"case{i}_b{barrier}"] = oracle_lib.fast10_list_reference(view, barrier)
+    np.savez_compressed(os.path.join(HERE, "fast_reference_cases.npz"), **c)
+    print(len(cases), "cases")
 
 
 if __name__ == "__main__":

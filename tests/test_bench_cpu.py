@@ -3,6 +3,8 @@ committed rocprofv3 PMC summary behind roofline.traffic, and the host-thread cen
 import json
 import os
 
+import numpy as np
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -169,3 +171,33 @@ def test_committed_profiles_describe_the_sources_in_the_tree():
     with open(os.path.join(ROOT, "profiles", "r06_bench_pmc.json")) as f:
         d = json.load(f)
     assert d["profile_source_sha"] == hip_build.source_sha(), "library sources changed after the committed profile run: re-run tools/profile.sh + merge_profiles.py"
+
+
+def test_dump_outputs_writes_every_returned_array_within_the_limit(tmp_path):
+    """--dump-outputs: the last step's poses, tracked counts and per-level statistics as float64 .npy files; over the limit a
+    fixed seeded sample of pairs (the same for every array, its indices in pair_index), never more bytes than the limit."""
+    import torch
+    from dsdtm_amd import capi
+    n = 1000
+    rng = np.random.default_rng(7)
+    st = np.zeros(n, capi.STATS_DTYPE)
+    st["iters"] = rng.integers(0, 11, st["iters"].shape)
+    st["chi2"] = rng.uniform(0, 1, st["chi2"].shape)
+    d = {"T_cur_w": torch.from_numpy(rng.normal(size=(n, 12))), "n_tracked": torch.from_numpy(rng.integers(0, 300, n).astype(np.int32)),
+         "stats": torch.from_numpy(st.view(np.uint8).reshape(n, -1).copy())}
+    bench.dump_outputs(str(tmp_path / "all"), d)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(got) == {"T_cur_w", "n_tracked"} | {"stats_" + k for k in capi.STATS_DTYPE.names}
+    assert all(a.dtype == np.float64 and len(a) == n for a in got.values())
+    assert np.array_equal(got["T_cur_w"], d["T_cur_w"].numpy().reshape(n, 3, 4)) and np.array_equal(got["n_tracked"], d["n_tracked"].numpy())
+    assert np.array_equal(got["stats_iters"], st["iters"]) and np.array_equal(got["stats_chi2"], st["chi2"])
+    limit = 64 << 10
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), d, limit=limit)
+    sizes = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    b = {p.stem: np.load(p) for p in (tmp_path / "b").iterdir()}
+    idx = a["pair_index"].astype(np.int64)
+    assert sizes <= limit and 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+    assert all(np.array_equal(a[k], b[k]) for k in a)                               # the sample is fixed
+    assert np.array_equal(a["T_cur_w"], got["T_cur_w"][idx]) and np.array_equal(a["stats_chi2"], got["stats_chi2"][idx])

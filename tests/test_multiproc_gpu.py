@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +22,7 @@ def test_bench_two_ranks_share_one_gpu():
     env["DSDTM_BENCH_SHARE_GPU"] = "1"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "64",
-                        "--preroll", "4", "--no-cpu", "--no-secondary"], env=env, capture_output=True, text=True, timeout=600)
+                        "--preroll", "4", "--full", "--no-cpu", "--no-secondary"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout                       # rank 0 alone prints
@@ -74,7 +75,7 @@ def test_bench_two_ranks_under_the_drivers_launcher():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "64",
-                        "--preroll", "4", "--no-cpu", "--no-secondary"], env=env, capture_output=True, text=True, timeout=600)
+                        "--preroll", "4", "--full", "--no-cpu", "--no-secondary"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -91,7 +92,7 @@ def test_bench_last_line_is_compact_with_every_secondary_entry():
     objects are in bench_secondary.json (round 4's 20 KB line was not parsed by the driver)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "64",
-                        "--cpu-sample", "8", "--preroll", "8"], env=env, capture_output=True, text=True, timeout=900)
+                        "--cpu-sample", "8", "--preroll", "8", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = r.stdout.splitlines()
     last = lines[-1]
@@ -116,3 +117,33 @@ def test_bench_last_line_is_compact_with_every_secondary_entry():
     with open(os.path.join(ROOT, "bench_secondary.json")) as f:
         full = json.load(f)
     assert len(full["secondary"]) == len(sec) and full["headline"]["roofline"]["kernel_time_basis"]
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline without the measurements and checks of --full;
+    --dump-outputs writes the last step's results, the same from run to run and the same as a --full run whose pose delta against
+    the CPU oracle passes on every pair."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    common = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "2", "--pairs", "64", "--preroll", "4"]
+    outs = {}
+    for name, extra in (("plain", ["--steps", "7"]), ("again", ["--steps", "3"]),
+                        ("full", ["--steps", "3", "--full", "--no-secondary", "--cpu-sample", "64"])):
+        r = subprocess.run(common + extra + ["--dump-outputs", str(tmp_path / name)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (name, r.stdout[-1000:], r.stderr[-3000:])
+        outs[name] = json.loads(r.stdout.splitlines()[-1])
+    plain = outs["plain"]
+    assert plain["steps"] == 7 and plain["warmup"] == 2 and plain["unit"] == "alignments/s" and plain["dtype"] == "f64"
+    assert plain["higher_is_better"] is True and plain["metric"] == outs["full"]["metric"]
+    assert plain["value"] > 0 and abs(plain["value"] - 64 * 7 / (plain["ms_per_step"] * 7e-3)) <= 2e-5 * plain["value"]
+    for k in ("roofline", "fp64", "cpu_baseline", "pose_delta_vs_cpu", "value_from_idle", "secondary", "err_vs_ground_truth_median"):
+        assert k not in plain, k
+    assert outs["full"]["pose_delta_vs_cpu"]["pairs_checked"] == 64 and outs["full"]["pose_delta_vs_cpu"]["max_rad"] <= 1e-4
+    names = sorted(p.name for p in (tmp_path / "plain").iterdir())
+    assert "T_cur_w.npy" in names and "n_tracked.npy" in names and "stats_iters.npy" in names
+    for n in names:
+        a = np.load(tmp_path / "plain" / n)
+        assert a.dtype == np.float64 and len(a) == 64, n
+        for other in ("again", "full"):
+            assert np.array_equal(a, np.load(tmp_path / other / n)), (n, other)
+    assert np.load(tmp_path / "plain" / "n_tracked.npy").mean() > 250

@@ -7,7 +7,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 label = sys.argv[-1] if len(sys.argv) > 1 else "lib"
-r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "20", "--no-cpu", "--no-secondary"],
+r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "200", "--warmup", "20", "--no-cpu", "--no-secondary"],
                    capture_output=True, text=True, timeout=280)
 line = [l for l in r.stdout.splitlines() if l.startswith("{")]
 if r.returncode or not line:

@@ -8,9 +8,9 @@ python - > $O/sha.txt <<'PY'
 import hashlib
 print("libdsdtm_amd.so sha256[:16] =", hashlib.sha256(open("dsdtm_amd/csrc/libdsdtm_amd.so", "rb").read()).hexdigest()[:16])
 PY
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench.json.log 2> $O/bench.err; echo "bench (driver-style) rc=$?"
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r06_bench.json.log 2> $O/bench.err; echo "bench (driver-style) rc=$?"
 cp bench_secondary.json $O/r06_bench_secondary.json
-timeout -k 10 600 python bench.py --no-secondary > $O/r06_bench_500.json.log 2>> $O/bench.err; echo "bench (500 steps) rc=$?"
+timeout -k 10 600 python bench.py --full --no-secondary > $O/r06_bench_500.json.log 2>> $O/bench.err; echo "bench (500 steps) rc=$?"
 ( cat $O/sha.txt
   echo "== soak_streamed";  timeout -k 10 400 python tools/soak_streamed.py 2>&1 | tail -4
   echo "== soak_duo";       timeout -k 10 300 python tools/soak_duo.py 2>&1 | tail -4

@@ -12,7 +12,7 @@ CASES="${2:-main solo n1000 n2000 kernels track trackone poseopt secondary}"
 has() { [[ " $CASES " == *" $1 "* ]]; }
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu --no-secondary"
+COMMON="--full --no-cpu --no-secondary"
 declare -A CASE
 CASE[main]="$REPO/bench.py --steps 200 --warmup 20 $COMMON"
 CASE[solo]="$REPO/bench.py --steps 200 --warmup 20 --streams 1 $COMMON"
@@ -25,7 +25,7 @@ CASE[trackone]="$REPO/tools/track_frame_bench.py"
 CASE[poseopt]="$REPO/tools/pose_opt_bench.py 4096 200 nolatency"
 # the driver's command WITH its secondary entries: the launch sizes the line's Align2D / FindMatchDirect / detector / single-pair
 # entries use (their roofline.traffic reads this case)
-CASE[secondary]="$REPO/bench.py --steps 5 --warmup 2 --preroll 0 --no-cpu"
+CASE[secondary]="$REPO/bench.py --full --steps 5 --warmup 2 --preroll 0 --no-cpu"
 for c in $CASES; do
   mkdir -p "$OUT/$c"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$c/trace" -- python3 ${CASE[$c]} > "$OUT/$c/trace.log" 2>&1 || echo "trace $c failed"

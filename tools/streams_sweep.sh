@@ -2,7 +2,7 @@
 # bench.py with 1..8 launch streams (same binary, same box): where do consecutive launches start to overlap?
 OUT=gpurun_out/${1:-sweep}; mkdir -p $OUT
 for s in 1 2 3 4 5 6 8; do
-  python bench.py --no-secondary --no-cpu --streams $s > $OUT/s$s.json 2> $OUT/s$s.err
+  python bench.py --full --no-secondary --no-cpu --streams $s > $OUT/s$s.json 2> $OUT/s$s.err
   python - <<PY
 import json
 d=json.loads(open("$OUT/s$s.json").read().strip().splitlines()[-1])

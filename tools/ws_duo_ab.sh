@@ -4,7 +4,7 @@
 export DSDTM_PY_DIAG=1   # the DSDTM_* switches below exist in the diagnostic library only (build.py --diag)
 REPO="$(cd "$(dirname "$0")/.." && pwd)"; cd "$REPO"
 O=gpurun_out/${1:-wsduo}; mkdir -p $O
-run() { timeout -k 10 120 python bench.py "$@" --steps 20 --warmup 3 --streams 1 --no-cpu --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%s: kernel %.4f ms  %.0f /s' % ('$LABEL', d['roofline']['kernel_ms_avg'], d['value']))"; }
+run() { timeout -k 10 120 python bench.py --full "$@" --steps 20 --warmup 3 --streams 1 --no-cpu --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%s: kernel %.4f ms  %.0f /s' % ('$LABEL', d['roofline']['kernel_ms_avg'], d['value']))"; }
 for rep in 1 2; do for nd in 1 0; do
   if [ $nd = 1 ]; then export DSDTM_WS_NO_DUO=1; else unset DSDTM_WS_NO_DUO; fi
   LABEL="no_duo $nd N=2000 1280x960 x256"; run --width 1280 --height 960 --patches 2000 --pairs 256 | tee -a $O/ab.txt
