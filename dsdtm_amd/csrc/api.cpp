@@ -1865,6 +1865,11 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
     memset(res, 0, sizeof *res);
     if (!d->image || d->width <= 0 || d->height <= 0 || d->stride < d->width || d->levels <= 0 || d->levels > DSDTM_MAX_LEVELS ||
         d->width > 16384 || d->height > 16384) { set_err(ctx, "track: bad image geometry"); return DSDTM_ERR_INVALID; }
+    // the grid, the packed mask (stride d->width) and the pyramid are sized by the image, the reprojection is bounded by the
+    // camera: a camera of another size would read the mask out of bounds (larger) or drop points silently (smaller)
+    if (cam->width != d->width || cam->height != d->height) {
+        set_err(ctx, "track: camera %dx%d does not match the image %dx%d", cam->width, cam->height, d->width, d->height); return DSDTM_ERR_INVALID;
+    }
     if (!d->ref || !d->T_ref_w || !d->T_seed || d->n_ref_features < 0 ||
         (d->n_ref_features > 0 && (!d->ref_px_xy || !d->ref_bearing || !d->ref_p_world || !d->ref_initial))) {
         set_err(ctx, "track: NULL reference-frame argument"); return DSDTM_ERR_INVALID;

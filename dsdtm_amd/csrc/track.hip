@@ -34,12 +34,14 @@ namespace dsdtm {
 
 namespace {
 
-// cvRound (OpenCV 2.4, SSE2 cvtsd2si): round half to even; callers have checked that v is finite and small
-__device__ __forceinline__ int cv_round(double v) { return (int)rint(v); }
+// cvRound of a cv::Point2f member (OpenCV 2.4, SSE2 cvtss2si): the reference builds the Point2f from the double pixel, so
+// the value is narrowed to float FIRST and then rounded half to even — a double within ~3e-5 of k + 0.5 becomes exactly
+// k + 0.5 and goes to the even neighbour. Callers have checked that v is finite and small.
+__device__ __forceinline__ int cv_round(double v) { return (int)rint((double)(float)v); }
 
 __device__ __forceinline__ bool in_image(int width, int height, double x, double y, int boundary, int level) {   // src/Camera.cpp:187-193
     if (!(fabs(x) < 1e9) || !(fabs(y) < 1e9)) return false;       // (NaN / infinity / beyond any image: cvRound is undefined there)
-    const int xr = cv_round(x), yr = cv_round(y);
+    const int xr = cv_round(x), yr = cv_round(y);                 // IsInImage(cv::Point2f, ..): rounds the narrowed pixel
     return xr >= boundary && xr < width / (1 << level) - boundary && yr >= boundary && yr < height / (1 << level) - boundary;
 }
 
@@ -110,7 +112,8 @@ __device__ __forceinline__ void reproject_point(const TrackArgs& a, int i, const
         a.ref_px[2 * (size_t)i] = 0.0f; a.ref_px[2 * (size_t)i + 1] = 0.0f; a.ref_level[i] = 0;
         a.ref_bearing[3 * (size_t)i] = 0.0; a.ref_bearing[3 * (size_t)i + 1] = 0.0; a.ref_bearing[3 * (size_t)i + 2] = 1.0;
     }
-    // the mask test of ReprojectCell (:96) reads the ROUNDED reprojected pixel; the caller's mask at the start of the search
+    // the mask test of ReprojectCell (:96) reads the reprojected pixel narrowed to cv::Point2f and rounded; the caller's mask
+    // at the start of the search
     uint8_t blocked = 0;
     if (in_grid && a.mask) blocked = a.mask[(size_t)cv_round(v) * a.mask_stride + cv_round(u)] != 255 ? 1 : 0;
     a.init_blocked[i] = blocked;
@@ -231,7 +234,7 @@ __global__ __launch_bounds__(NT) void track_replay_kernel(const TrackArgs a) {
     //         counting sort by cell, inside a cell by (found descending, list index) ----
     unsigned long long key[EPT];
     int kcell[EPT];
-    uint32_t cp[EPT], cq[EPT];          // rounded reprojected / refined pixel of the thread's candidates
+    uint32_t cp[EPT], cq[EPT];          // reprojected / refined pixel of the thread's candidates as cv::Point2f, rounded
     int csl[EPT];                       // search level; bit 8: live
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {

@@ -228,11 +228,14 @@ struct MapPoint {                                 // include/MapPoint.h (what th
 inline const std::array<double, 3>& Sprase_ImgAlign::map_point_pose(const MapPoint* mp) { return mp->Get_Pose(); }
 
 inline int cvRound(double v) { return (int)std::nearbyint(v); }      // OpenCV 2.4 cvRound: round half to even
-inline bool IsInImage(const Camera& c, double x, double y, int boundary, int level = 0) {   // src/Camera.cpp:187-193
+inline int cvRound(float v) { return (int)std::nearbyint(v); }       // (cvtss2si: the Point2f -> Point conversion)
+// src/Camera.cpp:187-193: IsInImage takes a cv::Point2f, so a double pixel is narrowed to float before it is rounded
+inline bool IsInImage(const Camera& c, float x, float y, int boundary, int level = 0) {
     return cvRound(x) >= boundary && cvRound(x) < c.mwidth / (1 << level) - boundary &&
            cvRound(y) >= boundary && cvRound(y) < c.mheight / (1 << level) - boundary;
 }
 inline void FillCircle(Image8& mask, int cx, int cy, int radius, uint8_t value);
+inline void SetMaskDisc(Image8& mask, const Feature& f, int radius);
 
 class Feature_Alignment {
 public:
@@ -248,7 +251,7 @@ public:
     void ResetGrid() { for (auto& c : mCells) c.clear(); }                            // :46-52
     bool ReprojectPoint(const Frame& tFrame, MapPoint* tMPoint) {                     // :54-69
         const std::array<double, 2> px = tFrame.World2Pixel(tMPoint->Get_Pose());
-        if (!(std::isfinite(px[0]) && std::isfinite(px[1]) && IsInImage(*mCam, px[0], px[1], 8))) return false;
+        if (!(std::fabs(px[0]) < 1e9 && std::fabs(px[1]) < 1e9 && IsInImage(*mCam, (float)px[0], (float)px[1], 8))) return false;   // (NaN / inf / far out: before narrowing)
         const int index = (int)(px[1] / Config::CellSize()) * mGrid_Cols + (int)(px[0] / Config::CellSize());
         mCells[(size_t)index].push_back(Candidate{tMPoint, px});
         return true;
@@ -358,13 +361,13 @@ public:
                 MapPoint* mp = cells[ci][pos].mp;
                 if (mp->IsBad()) continue;                                            // :93
                 const std::array<double, 2>& px = cells[ci][pos].px;
-                if (img_mask.data[(size_t)cvRound(px[1]) * img_mask.step + cvRound(px[0])] != 255) continue;   // :96
+                if (img_mask.data[(size_t)cvRound((float)px[1]) * img_mask.step + cvRound((float)px[0])] != 255) continue;   // :96 cv::Point2f(mPx)
                 const auto it = index.find({(int)ci, (int)pos});
                 if (it == index.end() || !conv[(size_t)it->second]) continue;         // :101-104
                 const int i = it->second;
                 const double x = pxr[2 * i] * (1 << sl[i]), y = pxr[2 * i + 1] * (1 << sl[i]);   // :154-156
                 mp->IncreaseFound();                                                  // :106
-                FillCircle(img_mask, cvRound(x), cvRound(y), Config::CellSize(), 0);  // :111
+                FillCircle(img_mask, cvRound((float)x), cvRound((float)y), Config::CellSize(), 0);  // :111 cv::Point2f(mPx)
                 Match mt; mt.cell = (int)ci; mt.mp = mp; mt.px[0] = (float)x; mt.px[1] = (float)y; mt.level = sl[i];
                 matches.push_back(mt);
                 Feature f; f.mpx_x = mt.px[0]; f.mpx_y = mt.px[1]; f.mlevel = mt.level;   // :108 new Feature(frame, px, level)
@@ -431,6 +434,10 @@ inline void FillCircle(Image8& mask, int cx, int cy, int radius, uint8_t value) 
     }
 }
 
+// Frame::Set_Mask (src/Frame.cpp:291): cv::circle(mImgMask, mvFeatures[k]->mpx, ..) converts the Point2f centre with cvRound,
+// half to even (2.5f -> 2, 3.5f -> 4)
+inline void SetMaskDisc(Image8& mask, const Feature& f, int radius) { FillCircle(mask, cvRound(f.mpx_x), cvRound(f.mpx_y), radius, 0); }
+
 struct Corner {                                   // include/Feature_detection.h:19-33
     int x, y, level;
     float score, angle;
@@ -481,7 +488,7 @@ public:
         std::fill(mask.data.begin(), mask.data.end(), 255);
         if (!frame->mvFeatures.empty()) {                                                        // :119-122, Frame::Set_Mask
             for (const Feature& f : frame->mvFeatures)
-                if (f.mbInitial) FillCircle(mask, (int)std::lround(f.mpx_x), (int)std::lround(f.mpx_y), Config::Min_dist(), 0);
+                if (f.mbInitial) SetMaskDisc(mask, f, Config::Min_dist());
             // src/Frame.cpp:294-296: threshold(mDynamicMask, 200) and the saturating mImgMask - mDynamicMask
             const Image8& dyn = frame->mDynamicMask;
             if (dyn.cols == mask.cols && dyn.rows == mask.rows)
@@ -631,7 +638,7 @@ public:
         for (int k = 0; k < r.n_matches; ++k) {
             MapPoint* mp = local_points[(size_t)ms[(size_t)k].point];
             mp->IncreaseFound();                                           // src/Feature_alignment.cpp:106
-            if (img_mask) FillCircle(*img_mask, cvRound((double)ms[(size_t)k].px[0]), cvRound((double)ms[(size_t)k].px[1]), Config::CellSize(), 0);   // :111
+            if (img_mask) FillCircle(*img_mask, cvRound(ms[(size_t)k].px[0]), cvRound(ms[(size_t)k].px[1]), Config::CellSize(), 0);   // :111
             Feature f; f.mpx_x = ms[(size_t)k].px[0]; f.mpx_y = ms[(size_t)k].px[1]; f.mlevel = ms[(size_t)k].level;   // :108
             f.Mpt = mp; f.mbInitial = true; f.mMptPose = mp->Get_Pose();    // :109
             cur->Add_Feature(f);                                           // :113-114

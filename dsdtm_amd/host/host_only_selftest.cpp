@@ -16,6 +16,18 @@ int main() {
     Camera cam; cam.mfx = cam.mfy = 500.0f; cam.mcx = 320.0f; cam.mcy = 240.0f; cam.mf = 525.0f; cam.mwidth = 640; cam.mheight = 480;
     assert(IsInImage(cam, 8.0, 8.0, 8) && !IsInImage(cam, 7.4, 8.0, 8) && !IsInImage(cam, 632.0, 100.0, 8) && IsInImage(cam, 631.4, 471.4, 8));
     assert(IsInImage(cam, 150.0, 100.0, 5, 2) && !IsInImage(cam, 156.0, 100.0, 5, 2));
+    // IsInImage takes a cv::Point2f: a double within ~3e-5 of k + 0.5 narrows to k + 0.5 and rounds to the even neighbour
+    assert(IsInImage(cam, 7.5 - 1e-9, 100.0, 8) && !IsInImage(cam, 631.5 - 1e-9, 100.0, 8));
+    assert(IsInImage(cam, 100.0, 7.5 - 1e-9, 8) && !IsInImage(cam, 100.0, 471.5 - 1e-9, 8));
+    // Frame::Set_Mask: the disc centre is cvRound(Point2f), half to even — a radius-0 disc is the centre pixel
+    {
+        Image8 m(8, 8);
+        std::fill(m.data.begin(), m.data.end(), 255);
+        Feature a; a.mpx_x = 2.5f; a.mpx_y = 3.5f;
+        SetMaskDisc(m, a, 0);
+        for (int y = 0; y < 8; ++y)
+            for (int x = 0; x < 8; ++x) assert((m.data[(size_t)y * m.step + x] == 0) == (x == 2 && y == 4));
+    }
     // discs at every border and far outside: nothing is written beyond the mask
     Image8 mask(64, 48);
     std::fill(mask.data.begin(), mask.data.end(), 255);

@@ -27,10 +27,17 @@ def cvRound(x: float) -> int:
     return int(np.rint(x))
 
 
+def cvRound_point2f(x: float) -> int:
+    """cvRound of a cv::Point2f member built from a double (SSE2 cvtss2si): the value is narrowed to float FIRST, so a
+    double within ~3e-5 of k + 0.5 becomes exactly k + 0.5 and rounds to the even neighbour."""
+    return int(np.rint(np.float32(x)))
+
+
 def is_in_image(cam, x: float, y: float, boundary: int, level: int = 0) -> bool:
-    """Camera::IsInImage (src/Camera.cpp:187-193)."""
-    return (cvRound(x) >= boundary and cvRound(x) < cam.width // (1 << level) - boundary and
-            cvRound(y) >= boundary and cvRound(y) < cam.height // (1 << level) - boundary)
+    """Camera::IsInImage (src/Camera.cpp:187-193): takes a cv::Point2f, so the pixel is narrowed to float and then rounded."""
+    xr, yr = cvRound_point2f(x), cvRound_point2f(y)
+    return (xr >= boundary and xr < cam.width // (1 << level) - boundary and
+            yr >= boundary and yr < cam.height // (1 << level) - boundary)
 
 
 def _circle_spans(radius: int):
@@ -254,14 +261,14 @@ class LocalPointSearch(FA.Feature_Alignment):
             for pos, (mp, px) in enumerate(cell):
                 if mp.IsBad():                                               # :93
                     continue
-                if img_mask[cvRound(px[1]), cvRound(px[0])] != 255:          # :96 (Point2f -> Point rounds)
+                if img_mask[cvRound_point2f(px[1]), cvRound_point2f(px[0])] != 255:   # :96 (cv::Point2f(mPx) -> Point rounds)
                     continue
                 r = results.get((ci, pos))
                 if r is None or not r[0]:                                    # :101-104
                     continue
                 ok, pxn, lvl = r
                 mp.IncreaseFound()                                           # :106
-                fill_circle(img_mask, cvRound(pxn[0]), cvRound(pxn[1]), self.mCell_size, 0)   # :111
+                fill_circle(img_mask, cvRound_point2f(pxn[0]), cvRound_point2f(pxn[1]), self.mCell_size, 0)   # :111
                 matches.append((ci, mp, pxn.astype(np.float32), lvl))        # Feature(px as Point2f, level)
                 n_matches += 1
                 break                                                        # :117 first success wins

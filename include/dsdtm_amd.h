@@ -352,8 +352,9 @@ int dsdtm_pose_optimization_batch_device(dsdtm_ctx* ctx, int n_frames, int max_f
  *
  * The device replay follows src/Feature_alignment.cpp:71-121 exactly: cells in index order (:75; mCellOrder is shuffled
  * but unused), per cell the candidates by Get_FoundNums() descending, stable in ReprojectPoint order (:88, :123-126), bad
- * points skipped (:93), the mask test on the ROUNDED reprojected pixel (:96), first success wins the cell (:115), a success
- * paints a disc of radius cell_size at the rounded REFINED pixel (:111, cv::circle's filled midpoint circle) which can
+ * points skipped (:93), the mask test on the reprojected pixel narrowed to float (cv::Point2f) and then rounded (:96), first
+ * success wins the cell (:115), a success paints a disc of radius cell_size at the rounded REFINED pixel (:111, cv::circle's
+ * filled midpoint circle) which can
  * suppress candidates of later cells, stop after max_matches matched cells (:80). The caller's list of map points is
  * the order ReprojectPoint would be called in (UpdateLocalMap walks the local keyframes' map points, :283-299); points the
  * reference never projects (NULL, already projected for this frame) are simply not in the list; bad ones may be (mp_bad).

@@ -40,9 +40,10 @@ def collect():
              warp_ref_level=w["ref_level"], warp_ref_px=w["ref_px"], warp_ref_bearing=w["ref_bearing"], warp_p_world=w["p_world"],
              warp_out_affine=aff, warp_out_level=sl, warp_out_border=pb, warp_out_patch=pp)
     for name in Q.SEARCH_WORLDS:                       # the worlds are seeded generators (640x480x5x4 images): outputs only
-        lst, mask = Q.search_restated(name)
+        lst, mask, n_in = Q.search_restated(name)
         d[f"search_{name}_matches"] = np.array(lst, np.float64).reshape(-1, 5)
         d[f"search_{name}_mask_rows"] = np.packbits(mask == 255, axis=1)
+        d[f"search_{name}_n_in_grid"] = np.array(n_in)
     return d
 
 

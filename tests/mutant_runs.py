@@ -59,6 +59,8 @@ TABLE = {
     "S1_ALLCANDS":     ("search:dense", "cells", "S1", "src/Feature_alignment.cpp:115"),
     "W3_BORDER":       ("search:dense_border", "cells", "W3", "src/Feature_alignment.cpp:138-140"),
     "W3_FIRSTOBS":     ("search:std", "match count", "W3", "src/MapPoint.cpp:148-171"),
+    "S1_ROUND_BORDER": ("search:round", "match count", "S1", "src/Feature_alignment.cpp:58, src/Camera.cpp:187-193"),
+    "S1_ROUND_MASK":   ("search:round", "cells", "S1", "src/Feature_alignment.cpp:96"),
 }
 
 ALL_MUTANTS = list(TABLE)

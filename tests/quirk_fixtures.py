@@ -233,7 +233,28 @@ SEARCH_WORLDS = {
     "std": dict(seed=3, n_points=900, cell=25),
     "dense": dict(seed=5, n_points=2000, cell=15, obs_margin=3),
     "dense_border": dict(seed=5, n_points=2000, cell=15, obs_margin=3, uv_margin=4),
+    "round": dict(seed=3, n_points=900, cell=25, plants=True),
 }
+
+# The "round" world: the std world plus map points PLANTED at chosen pixels of the current frame (make_world(uv_cur=)) within
+# 1e-9..1e-7 of k + 0.5, where a cv::Point2f (the double narrowed to float, then rounded half to even) and the double rounded
+# directly give neighbouring integers. (kind, x, y, what the faithful rounding decides there):
+#   border   ReprojectPoint's IsInImage(cv::Point2f(tPx), 8) (src/Feature_alignment.cpp:58): 7.5 - e is IN the grid (-> 8),
+#            631.5 - e / 471.5 - e are OUT (-> 632 / 472); the double says the opposite
+#   mask     the mask test of ReprojectCell (:96) against ROUND_BLOCKED, single blocked pixels of the caller's mask: exactly one
+#            of the two roundings lands on the blocked pixel
+#   disc     the mask test against the edge of a disc an earlier cell painted (:111): one rounding lands inside it
+# tests/test_search_restatement_cpu.py checks that each plant still sits where the two roundings part.
+ROUND_PLANTS = [
+    ("border", 7.499999999, 40.25, "in"), ("border", 7.49999997, 151.25, "in"), ("border", 7.4999999, 373.25, "in"),
+    ("border", 86.25, 7.499999997, "in"), ("border", 373.25, 7.49999997, "in"),
+    ("border", 631.4999999, 114.25, "out"), ("border", 631.49999997, 262.25, "out"), ("border", 250.25, 471.4999999, "out"),
+    ("mask", 60.500001, 172.25, "blocked"), ("mask", 107.499999999, 50.25, "free"), ("mask", 60.5000001, 355.25, "free"),
+    ("mask", 107.4999999, 294.25, "free"),
+    ("disc", 619.49999999, 131.25, "free"), ("disc", 573.499999999, 136.25, "blocked"), ("disc", 244.50000001, 430.25, "blocked"),
+    ("disc", 119.49999999, 144.25, "free"),
+]
+ROUND_BLOCKED = [(60, 172), (107, 50), (61, 355), (107, 294)]     # (x, y): one blocked pixel per mask plant
 
 
 def search_world(name):
@@ -243,32 +264,47 @@ def search_world(name):
     kw = dict(SEARCH_WORLDS[name])
     Config.Set("Camera.CellSize", kw["cell"])
     Config.Set("Camera.MaxPyraLevels", 5)
+    if kw.pop("plants", False):
+        kw["uv_cur"] = [(p[1], p[2]) for p in ROUND_PLANTS]
     cam, kfs, cur, mps = make_world(kw.pop("seed"), **kw)
     return cam, kfs, cur, mps, kw["cell"]
 
 
-def search_restated(name, mutant=None):
-    """The sequential CPU restatement (tests/search_restatement.py) on a named world: ([(cell, map point index, px, level)], mask)."""
-    from dsdtm_amd import search
+def search_mask(name):
+    """Frame::mImgMask at the start of the search in a named world (255 = free)."""
+    mask = np.full((480, 640), 255, np.uint8)
+    if SEARCH_WORLDS[name].get("plants"):
+        for x, y in ROUND_BLOCKED:
+            mask[y, x] = 0
+    return mask
+
+
+def search_restated(name, mutant=None, trace=None, mask=None):
+    """The sequential CPU restatement (tests/search_restatement.py) on a named world, grid included (its own ReprojectPoint),
+    from the world's mask (search_mask) or `mask`: ([(cell, map point index, px, level)], final mask, number of live (not bad)
+    map points in the grid)."""
     from tests import search_restatement as SR
     cam, kfs, cur, mps, cell = search_world(name)
-    s = search.LocalPointSearch.__new__(search.LocalPointSearch)         # the grid bookkeeping only: no GPU context
-    search.FA.Feature_Alignment.__init__(s, cam, None)
-    s.mCell_size = cell
-    s.mGrid_Rows, s.mGrid_Cols = int(np.ceil(cam.height / cell)), int(np.ceil(cam.width / cell))
-    s.mCells = [[] for _ in range(s.mGrid_Rows * s.mGrid_Cols)]
+    cols = int(np.ceil(cam.width / cell))
+    cells = [[] for _ in range(int(np.ceil(cam.height / cell)) * cols)]
+    n_in = 0
     for mp in mps:
-        s.ReprojectPoint(cur, mp)
-    mask = np.full((cam.height, cam.width), 255, np.uint8)
+        r = SR.reproject_point(cam, cur.Get_Pose(), mp.mPose, cell, cols, mutant=mutant)
+        if r is not None:
+            cells[r[0]].append([mp, r[1]])
+            n_in += 0 if mp.mbBad else 1
+    mask = search_mask(name) if mask is None else np.array(mask, np.uint8)
     idx = {id(mp): i for i, mp in enumerate(mps)}
-    out = SR.search_local_points(s.mCells, cur, kfs, cam, cell, 5, mask, mutant=mutant)
-    return [(int(o[0]), idx[id(o[1])], float(o[2][0]), float(o[2][1]), int(o[3])) for o in out], mask
+    out = SR.search_local_points(cells, cur, kfs, cam, cell, 5, mask, mutant=mutant, trace=trace)
+    if trace is not None:
+        trace[:] = [(t[0], idx[id(t[1])], *t[2:]) for t in trace]
+    return [(int(o[0]), idx[id(o[1])], float(o[2][0]), float(o[2][1]), int(o[3])) for o in out], mask, n_in
 
 
 def search_first_difference(a, b):
-    """a, b = (match list, mask): same cells in the same order, same map point, level and refined pixel per cell, same mask
-    (tests/test_search_gpu.py::test_search_local_points_matches_sequential_reference_flow)."""
-    (la, ma), (lb, mb) = a, b
+    """a, b = (match list, mask, grid count): same cells in the same order, same map point, level and refined pixel per cell,
+    same mask, same number of live points in the grid (tests/test_search_gpu.py::test_search_local_points_matches_sequential_reference_flow)."""
+    (la, ma, na), (lb, mb, nb) = a, b
     if len(la) != len(lb):
         return "match count"
     if [x[0] for x in la] != [x[0] for x in lb]:
@@ -281,6 +317,8 @@ def search_first_difference(a, b):
         return "px"
     if not np.array_equal(ma, mb):
         return "mask"
+    if na != nb:
+        return "grid count"
     return None
 
 

@@ -8,12 +8,37 @@ from tests import oracle_lib
 
 
 def cv_round(x):
+    """cvRound of a cv::Point2f member: the reference builds the Point2f from a double, so the value is narrowed to float
+    first; np.rint on float32 rounds half to even like cvtss2si."""
+    return int(np.rint(np.float32(x)))
+
+
+def cv_round_double(x):
+    """cvRound of the double itself (cvtsd2si): what the S1_ROUND_* mutants do."""
     return int(np.rint(x))
 
 
-def in_image(cam, x, y, b, lvl=0):
-    return (cv_round(x) >= b and cv_round(x) < cam.width // (1 << lvl) - b and
-            cv_round(y) >= b and cv_round(y) < cam.height // (1 << lvl) - b)
+def in_image(cam, x, y, b, lvl=0, rnd=cv_round):
+    """Camera::IsInImage(cv::Point2f, b, level) (src/Camera.cpp:187-193)."""
+    return (rnd(x) >= b and rnd(x) < cam.width // (1 << lvl) - b and
+            rnd(y) >= b and rnd(y) < cam.height // (1 << lvl) - b)
+
+
+def reproject_point(cam, T_cw, P, cell, cols, mutant=None):
+    """Feature_Alignment::ReprojectPoint (src/Feature_alignment.cpp:54-69): Frame::World2Pixel (src/Frame.cpp:318-323,
+    Camera::Camera2Pixel src/Camera.cpp:167-171) in double, IsInImage(cv::Point2f(tPx), 8), the cell from the DOUBLE pixel
+    (:62-63). Returns (cell index, px) or None."""
+    T = np.asarray(T_cw, np.float64)
+    x = T[0, 0] * P[0] + T[0, 1] * P[1] + T[0, 2] * P[2] + T[0, 3]
+    y = T[1, 0] * P[0] + T[1, 1] * P[1] + T[1, 2] * P[2] + T[1, 3]
+    z = T[2, 0] * P[0] + T[2, 1] * P[1] + T[2, 2] * P[2] + T[2, 3]
+    with np.errstate(all="ignore"):
+        u, v = float(cam.fx) * x / z + float(cam.cx), float(cam.fy) * y / z + float(cam.cy)
+    if not (abs(u) < 1e9 and abs(v) < 1e9):
+        return None
+    if not in_image(cam, u, v, 8, rnd=cv_round_double if mutant == "S1_ROUND_BORDER" else cv_round):
+        return None
+    return int(v / cell) * cols + int(u / cell), np.array([u, v], np.float64)
 
 
 def circle_filled(mask, cx, cy, r):
@@ -46,11 +71,15 @@ SEARCH_MUTANTS = {
     "S1_ALLCANDS": "no break after the first success in a cell (:115)",
     "W3_BORDER": "reference pixel kept 8 px (the grid's border, :62) instead of 5 px inside its level image (:138-140)",
     "W3_FIRSTOBS": "the first observation instead of the closest view (src/MapPoint.cpp:148-171)",
+    "S1_ROUND_BORDER": "ReprojectPoint's IsInImage rounds the double pixel instead of the cv::Point2f (:58)",
+    "S1_ROUND_MASK": "the mask test rounds the double pixel instead of cv::Point2f(mPx) (:96)",
 }
 
 
-def search_local_points(cells, frame, keyframes, cam, cell_size, max_levels, mask, mutant=None):
-    """cells: list of lists of [MapPoint, px]. Returns [(cell, mp, px float32, level)]."""
+def search_local_points(cells, frame, keyframes, cam, cell_size, max_levels, mask, mutant=None, trace=None):
+    """cells: list of lists of [MapPoint, px]. Returns [(cell, mp, px float32, level)]. `trace` (a list): gets one
+    (cell, mp, px, blocked as cv::Point2f, blocked as double) per candidate that reaches the mask test (:96), with the mask
+    as it is at that moment."""
     assert mutant is None or mutant in SEARCH_MUTANTS, mutant
     out = []
     matches = 0
@@ -65,7 +94,11 @@ def search_local_points(cells, frame, keyframes, cam, cell_size, max_levels, mas
             mp, px = cand
             if mp.mbBad and mutant != "S1_NOBAD":
                 continue
-            if mask[cv_round(px[1]), cv_round(px[0])] != 255 and mutant != "S1_NOMASK":
+            rnd = cv_round_double if mutant == "S1_ROUND_MASK" else cv_round
+            if trace is not None:
+                trace.append((ci, mp, px.copy(), bool(mask[cv_round(px[1]), cv_round(px[0])] != 255),
+                              bool(mask[cv_round_double(px[1]), cv_round_double(px[0])] != 255)))
+            if mask[rnd(px[1]), rnd(px[0])] != 255 and mutant != "S1_NOMASK":
                 continue
             # --- FindMatchDirect ---
             if not mp.mObservations:

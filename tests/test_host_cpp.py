@@ -111,22 +111,30 @@ def dump_world(path, cam, kfs, cur, mps, levels, cell, max_levels, frames=()):
 
 
 @pytest.mark.gpu
-def test_cpp_search_local_points_matches_the_python_mirror(tmp_path, gpu_ctx):
+@pytest.mark.parametrize("world_name", ["seed5", "round"])
+def test_cpp_search_local_points_matches_the_python_mirror(tmp_path, gpu_ctx, world_name):
     """Feature_Alignment::ResetGrid / ReprojectPoint / SearchLocalPoints of the C++ layer against
     dsdtm_amd.search.LocalPointSearch (itself held to the sequential restatement in test_search_gpu.py):
-    same library calls underneath, so cells, map points, levels, pixels and the mask agree exactly."""
+    same library calls underneath, so cells, map points, levels, pixels and the mask agree exactly. On the quirk world "round"
+    (map points planted where a cv::Point2f and the double round apart: the grid border, the edges of match discs) both are
+    also held to the sequential restatement from the same all-free mask."""
     from dsdtm_amd import search
     from dsdtm_amd.frame import Config
+    from tests import quirk_fixtures as Q
     from tests.test_search_gpu import make_world
     exe = build_example("example_search")
     Config.Set("Camera.CellSize", 25); Config.Set("Camera.MaxPyraLevels", 5)
-    cam, kfs, cur, mps = make_world(5, n_points=700)
+    if world_name == "round":
+        cam, kfs, cur, mps, _ = Q.search_world("round")
+    else:
+        cam, kfs, cur, mps = make_world(5, n_points=700)
     world = tmp_path / "world.bin"
     dump_world(world, cam, kfs, cur, mps, 5, 25, 5)
     out = subprocess.run([exe, str(world)], capture_output=True, text=True, check=True).stdout.strip().split("\n")
     s = search.LocalPointSearch(cam, ctx=gpu_ctx)
     s.ResetGrid()
-    n_in = sum(s.ReprojectPoint(cur, mp) for mp in mps)
+    in_grid = [s.ReprojectPoint(cur, mp) for mp in mps]
+    n_in = sum(in_grid)
     mask = np.full((cam.height, cam.width), 255, np.uint8)
     got = s.SearchLocalPoints(cur, kfs, mask)
     assert int(out[0].split()[1]) == n_in and int(out[1].split()[1]) == len(got) and len(got) > 100
@@ -137,6 +145,11 @@ def test_cpp_search_local_points_matches_the_python_mirror(tmp_path, gpu_ctx):
         assert np.float32(x) == g[2][0] and np.float32(y) == g[2][1]
     assert int(out[2 + len(got)].split()[1]) == int(mask.astype(np.uint64).sum())
     assert out[3 + len(got)].split() == ["resident_same", "1"]         # device-resident frames: one library call, same matches
+    if world_name == "round":
+        want, want_mask, want_n = Q.search_restated("round", mask=np.full((cam.height, cam.width), 255, np.uint8))
+        assert [(g[0], idx[id(g[1])], float(g[2][0]), float(g[2][1]), g[3]) for g in got] == want
+        assert np.array_equal(mask, want_mask)
+        assert sum(1 for mp, i in zip(mps, in_grid) if i and not mp.IsBad()) == want_n
 
 
 @pytest.mark.gpu

@@ -42,9 +42,10 @@ def test_faithful_oracle_reproduces_the_committed_outputs(faithful, golden):
     for i, k in enumerate(("warp_out_affine", "warp_out_level", "warp_out_border", "warp_out_patch")):
         assert np.array_equal(faithful["warp"][i], golden[k]), k
     for name in Q.SEARCH_WORLDS:
-        lst, mask = faithful["search:" + name]
+        lst, mask, n_in = faithful["search:" + name]
         assert np.array_equal(np.array(lst, np.float64).reshape(-1, 5), golden[f"search_{name}_matches"])
         assert np.array_equal(np.packbits(mask == 255, axis=1), golden[f"search_{name}_mask_rows"])
+        assert n_in == int(golden[f"search_{name}_n_in_grid"])
 
 
 def test_the_fixtures_reach_what_they_are_for(faithful):

@@ -51,15 +51,17 @@ def gpu_detect_cells(ctx, pyr, levels, cell, cols, rows, occupied, thr):
 
 
 def gpu_search(ctx, name):
+    """The four-call chain on a named world from the world's mask: (match list, final mask, live points in the grid)."""
     cam, kfs, cur, mps, cell = Q.search_world(name)
     s = search.LocalPointSearch(cam, ctx=ctx)
     s.ResetGrid()
+    n_in = 0
     for mp in mps:
-        s.ReprojectPoint(cur, mp)
-    mask = np.full((cam.height, cam.width), 255, np.uint8)
+        n_in += 1 if s.ReprojectPoint(cur, mp) and not mp.IsBad() else 0
+    mask = Q.search_mask(name)
     idx = {id(mp): i for i, mp in enumerate(mps)}
     got = s.SearchLocalPoints(cur, kfs, mask)
-    return [(int(g[0]), idx[id(g[1])], float(g[2][0]), float(g[2][1]), int(g[3])) for g in got], mask
+    return [(int(g[0]), idx[id(g[1])], float(g[2][0]), float(g[2][1]), int(g[3])) for g in got], mask, n_in
 
 
 @pytest.fixture(scope="module")
@@ -108,9 +110,10 @@ def test_hip_path_agrees_with_the_committed_outputs(hip):
     for i, k in enumerate(("warp_out_affine", "warp_out_level", "warp_out_border", "warp_out_patch")):
         assert np.array_equal(hip["warp"][i], g[k]), k
     for name in Q.SEARCH_WORLDS:
-        lst, mask = hip["search:" + name]
+        lst, mask, n_in = hip["search:" + name]
         assert np.array_equal(np.array(lst, np.float64).reshape(-1, 5), g[f"search_{name}_matches"]), name
         assert np.array_equal(np.packbits(mask == 255, axis=1), g[f"search_{name}_mask_rows"]), name
+        assert n_in == int(g[f"search_{name}_n_in_grid"]), name
 
 
 @pytest.mark.parametrize("mutant", M.ALL_MUTANTS)

@@ -9,10 +9,14 @@ from dsdtm_amd.frame import Config, Frame
 from tests import search_restatement as SR
 
 
-def make_world(seed, n_points=900, n_kf=3, width=640, height=480, cell=25, obs_margin=12, uv_margin=20, tex=None, cam=None, uv=None):
+def make_world(seed, n_points=900, n_kf=3, width=640, height=480, cell=25, obs_margin=12, uv_margin=20, tex=None, cam=None, uv=None,
+               uv_cur=None, found_cur=100):
     """A textured plane seen by n_kf keyframes and one current frame; map points on the plane with
     observations in the keyframes. `tex` (a real image), `cam` and `uv` (where on the first keyframe's image the map points sit,
-    e.g. a detector's corners) replace the seeded texture, the TUM intrinsics and the uniform draw."""
+    e.g. a detector's corners) replace the seeded texture, the TUM intrinsics and the uniform draw. `uv_cur` PLANTS further map
+    points after those: where the ray of each pixel of the CURRENT frame meets the plane, so that World2Pixel gives that pixel
+    back to ~1e-13; they are observed at level 0 by every keyframe that sees them inside obs_margin, are never bad and have
+    found count `found_cur` (first in their cell)."""
     rng = np.random.default_rng(seed)
     cam = synth.Camera.tum(width, height) if cam is None else cam
     tex = synth.make_texture(height, width, seed) if tex is None else np.asarray(tex, np.float64)
@@ -41,6 +45,19 @@ def make_world(seed, n_points=900, n_kf=3, width=640, height=480, cell=25, obs_m
                     obs[k] = len(feats[k])
                     feats[k].append((px.astype(np.float32), lvl))
         mps.append(search.MapPoint(P[i].copy(), obs, mnFound=int(rng.integers(1, 6)), mbBad=bool(rng.random() < 0.03)))
+    if uv_cur is not None:
+        T = poses[n_kf]
+        C = -T[:3, :3].T @ T[:3, 3]
+        for u, v in np.asarray(uv_cur, np.float64).reshape(-1, 2):
+            d = T[:3, :3].T @ np.array([(u - cam.cx) / cam.fx, (v - cam.cy) / cam.fy, 1.0])
+            Pp = C + (depth - C[2]) / d[2] * d
+            obs = {}
+            for k in range(n_kf):
+                px = kfs[k].World2Pixel(Pp)
+                if obs_margin < px[0] < width - obs_margin and obs_margin < px[1] < height - obs_margin:
+                    obs[k] = len(feats[k])
+                    feats[k].append((px.astype(np.float32), 0))
+            mps.append(search.MapPoint(Pp, obs, mnFound=int(found_cur)))
     for k in range(n_kf):
         px = np.array([f[0] for f in feats[k]], np.float32).reshape(-1, 2)
         kfs[k].set_features(px, synth.bearing_from_px(cam, px), np.zeros((len(px), 3)), np.ones(len(px), np.uint8),

@@ -26,18 +26,20 @@ pytestmark = pytest.mark.gpu
 
 def track_search(ctx, name, **kw):
     """A named search world through dsdtm_track_frame with Run switched off (no reference features, min_tracked 0: the pose stays
-    the seed = the world's current pose): (match list, mask painted from it) in the shape of quirk_fixtures.search_restated."""
+    the seed = the world's current pose), from the world's mask: (match list, mask painted from it, live points in the grid, the
+    result) — the first three in the shape of quirk_fixtures.search_restated."""
     cam, kfs, cur, mps, cell = Q.search_world(name)
     last = Frame(cam, cur.mvImg_Pyr, cur.Get_Pose())            # any resident frame of the geometry; it has no features: Run returns 0
+    mask0 = Q.search_mask(name)
     r = tracking.track_frame(ctx, cam, cur.mvImg_Pyr[0], 5, last, cur.Get_Pose(), (5, 0, 8, 15), 0, kfs, mps, cell_size=cell,
-                             max_pyr_levels=5, **kw)
+                             max_pyr_levels=5, mask=mask0.copy(), **kw)
     assert r["n_tracked"] == 0 and not r["lost"] and np.array_equal(r["T_run"], cur.Get_Pose())
-    mask = np.full((cam.height, cam.width), 255, np.uint8)
+    mask = mask0.copy()
     m = r["matches"]
     for q in m["px"]:
         search.fill_circle(mask, search.cvRound(float(q[0])), search.cvRound(float(q[1])), cell, 0)
     r["frame"].close()
-    return [(int(m["cell"][k]), int(m["point"][k]), float(m["px"][k][0]), float(m["px"][k][1]), int(m["level"][k])) for k in range(len(m))], mask, r
+    return [(int(m["cell"][k]), int(m["point"][k]), float(m["px"][k][0]), float(m["px"][k][1]), int(m["level"][k])) for k in range(len(m))], mask, int(r["n_in_grid"]), r
 
 
 @pytest.fixture(scope="module")
@@ -47,14 +49,16 @@ def track_outputs(gpu_ctx):
 
 @pytest.mark.parametrize("name", list(Q.SEARCH_WORLDS))
 def test_device_replay_equals_the_sequential_restatement(track_outputs, name):
-    lst, mask, r = track_outputs[name]
+    lst, mask, n_in, r = track_outputs[name]
     want = Q.search_restated(name)
-    assert Q.search_first_difference(want, (lst, mask)) is None
+    assert Q.search_first_difference(want, (lst, mask, n_in)) is None
+    assert r["n_in_grid"] == want[2]
     assert len(lst) >= 150 and len(lst) <= 200 and r["n_in_grid"] > 500
     # and the committed outputs of the four-call chain (tests/golden/quirks.npz)
     g = np.load(H.golden_path("quirks.npz"))
     assert np.array_equal(np.array(lst, np.float64).reshape(-1, 5), g[f"search_{name}_matches"])
     assert np.array_equal(np.packbits(mask == 255, axis=1), g[f"search_{name}_mask_rows"])
+    assert n_in == int(g[f"search_{name}_n_in_grid"])
 
 
 @pytest.mark.parametrize("mutant", [m for m in M.ALL_MUTANTS if M.domain(m) == "search"])
@@ -62,8 +66,8 @@ def test_device_replay_disagrees_with_every_search_mutant(track_outputs, mutant)
     case, check, quirk, cite = M.TABLE[mutant]
     name = case.split(":")[1]
     out = M.cpu_outputs(mutant, domains=("search",), search_worlds=[name])
-    lst, mask, _ = track_outputs[name]
-    got = Q.search_first_difference(out[case], (lst, mask))
+    lst, mask, n_in, _ = track_outputs[name]
+    got = Q.search_first_difference(out[case], (lst, mask, n_in))
     assert got == check, f"{mutant} ({quirk}, {cite}): {got!r} for the device replay against this mutant, expected {check!r}"
 
 
@@ -420,6 +424,12 @@ def test_argument_checks(gpu_ctx):
     small = Frame(synth.Camera.tum(320, 240), synth.build_pyramid(cur.mvImg_Pyr[1], 5), cur.Get_Pose())
     with pytest.raises(capi.DsdtmError):
         tracking.track_frame(gpu_ctx, cam, cur.mvImg_Pyr[0], 5, small, cur.Get_Pose(), (5, 0, 8, 15), 0, kfs, mps)
+    # a camera larger or smaller than the image (the grid, the mask and the pyramid follow the image): rejected on the host
+    for w, h in ((cam.width + 16, cam.height), (cam.width, cam.height - 16)):
+        other = synth.Camera(cam.fx, cam.fy, cam.cx, cam.cy, cam.f, w, h)
+        with pytest.raises(capi.DsdtmError) as e:
+            tracking.track_frame(gpu_ctx, other, cur.mvImg_Pyr[0], 5, last, cur.Get_Pose(), (5, 0, 8, 15), 0, kfs, mps)
+        assert e.value.status == capi.ERR_INVALID and "does not match the image" in str(e.value), (w, h)
     # and the context still works
     ok()["frame"].close()
 
