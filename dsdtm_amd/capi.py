@@ -141,6 +141,7 @@ EXPORTED_SYMBOLS = [
     "dsdtm_pose_optimization", "dsdtm_pose_optimization_batch_device",
     "dsdtm_sparse_align_batch_sharded", "dsdtm_sparse_align_batch_streamed", "dsdtm_shard_range", "dsdtm_detect_cells_batch_device",
     "dsdtm_match_candidates_batch_device", "dsdtm_match_candidates_scratch_bytes", "dsdtm_track_frame",
+    "dsdtm_track_frames",
 ]
 
 
@@ -315,6 +316,9 @@ def load(diag: bool | None = None):
                                                       C.POINTER(AlignParams)]
     lib.dsdtm_track_frame.restype = C.c_int
     lib.dsdtm_track_frame.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(TrackDesc), C.POINTER(TrackResult), C.c_void_p, C.c_void_p]
+    lib.dsdtm_track_frames.restype = C.c_int
+    lib.dsdtm_track_frames.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.POINTER(TrackDesc), C.POINTER(TrackResult), C.c_void_p,
+                                       C.c_void_p, C.c_void_p]
     lib.dsdtm_shard_range.restype = None
     lib.dsdtm_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if diag:

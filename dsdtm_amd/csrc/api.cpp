@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -100,8 +101,7 @@ struct dsdtm_ctx {
 // Contexts that are alive (dsdtm_frame_destroy may be handed a context that is already gone: it must not be dereferenced)
 static std::mutex g_live_mutex;
 static std::vector<dsdtm_ctx*> g_live_ctx;
-static bool ctx_is_live(dsdtm_ctx* ctx) {
-    std::lock_guard<std::mutex> g(g_live_mutex);
+static bool ctx_is_live_locked(dsdtm_ctx* ctx) {      // (g_live_mutex held)
     for (dsdtm_ctx* c : g_live_ctx) if (c == ctx) return true;
     return false;
 }
@@ -371,6 +371,8 @@ static constexpr int g_team_drop_members = 0;
 struct LaunchMode {
     bool one_cu = false;        // never a team / two-member kernel (re-runs after a timeout, captured launches)
     bool single = false;        // synchronous single-pair entry: its own timeout word, settled by the caller itself
+    int variant = -1;           // >= 0: this register variant, whatever max_features (dsdtm_track_frames: max_features is a stride)
+    const uint8_t* const* ref_ptrs = nullptr;   // device table of the pairs' reference pyramids (dsdtm_track_frames)
 };
 static int launch_batch(dsdtm_ctx* ctx, const dsdtm_batch_desc* b, const dsdtm_camera* cam, const dsdtm_align_params* prm,
                         void* hip_stream, const LaunchMode& mode, bool* multi_cu_used);
@@ -545,8 +547,9 @@ static int launch_batch(dsdtm_ctx* ctx, const dsdtm_batch_desc* b, const dsdtm_c
     // replay could neither be ordered against live team launches nor be re-run after a timeout).
     const bool multi_cu = ctx->multi_cu_ok && !mode.one_cu && !capturing;
     const int team_k = (multi_cu && b->n_pairs <= 64 && !options().no_team) ? sparse_align_team_size(b->n_pairs, b->max_features, ctx->num_cus) : 0;
-    const SAVariant v = sparse_align_pick_variant(b->max_features);
-    const size_t ws = sparse_align_workspace_bytes(b->n_pairs, b->max_features);
+    const SAVariant v = mode.variant >= 0 ? (SAVariant)mode.variant : sparse_align_pick_variant(b->max_features);
+    const size_t ws = mode.variant >= 0 ? 0 : sparse_align_workspace_bytes(b->n_pairs, b->max_features);
+    a.ref_ptrs = mode.ref_ptrs;
     const bool duo = !team_k && multi_cu && sparse_align_uses_duo(b->max_features, ws != 0);
     int slot = -1;
     if ((team_k || duo) && !mode.single) {
@@ -1150,25 +1153,54 @@ extern "C" int dsdtm_sparse_align(dsdtm_ctx* ctx, const dsdtm_pyramid* ref, cons
 }
 
 // ---- frames that stay on the device --------------------------------------------------------------
+// The frames of one dsdtm_track_frames call share one allocation (a slab: frame i at i * pitch, so that the batch kernels
+// address them as packed pyramids); the slab is released when its last frame is destroyed.
+struct FrameSlab {
+    dsdtm_ctx* owner;
+    int device;
+    uint8_t* d;
+    size_t bytes;
+    std::atomic<int> refs;
+};
+
 struct dsdtm_frame {
     dsdtm_ctx* owner;    // compared only, never dereferenced through the frame (a frame may outlive its context)
     int device;
-    uint8_t* d;          // packed pyramid (the layout of plan_pyramid), its own allocation
+    uint8_t* d;          // packed pyramid (the layout of plan_pyramid), its own allocation or a place in `slab`
     size_t pitch;
     PackedPyr pl;
+    FrameSlab* slab = nullptr;
 };
+
+// The frame pool is shared with dsdtm_frame_destroy, which may run on any thread (a garbage collector's): it is touched only
+// under g_live_mutex, held across the liveness check of the context — dsdtm_destroy takes a context off the live list under
+// the same lock before it frees the pool.
+static uint8_t* pool_take(dsdtm_ctx* ctx, size_t bytes) {
+    std::lock_guard<std::mutex> g(g_live_mutex);
+    for (size_t i = 0; i < ctx->frame_pool.size(); ++i)
+        if (ctx->frame_pool[i].pitch == bytes) {                // a destroyed frame's buffer of this size (its users have drained:
+            uint8_t* d = ctx->frame_pool[i].d;                  // every entry that takes a dsdtm_frame waits for its stream)
+            ctx->frame_pool.erase(ctx->frame_pool.begin() + (long)i);
+            return d;
+        }
+    return nullptr;
+}
+
+// its own, LIVE context on the same device: the buffer goes to that context's pool (no hipFree, which would wait for the whole
+// device); false: the caller frees it
+static bool pool_give(dsdtm_ctx* ctx, dsdtm_ctx* owner, int device, uint8_t* d, size_t bytes) {
+    if (!ctx || !d || owner != ctx) return false;
+    std::lock_guard<std::mutex> g(g_live_mutex);
+    if (!ctx_is_live_locked(ctx) || ctx->device != device || ctx->frame_pool.size() >= dsdtm_ctx::FRAME_POOL) return false;
+    try { ctx->frame_pool.push_back(dsdtm_ctx::PooledFrame{bytes, d}); } catch (...) { return false; }
+    return true;
+}
 
 static int frame_alloc(dsdtm_ctx* ctx, const PackedPyr& pl, dsdtm_frame** out) {
     dsdtm_frame* f = new (std::nothrow) dsdtm_frame();
     if (!f) return DSDTM_ERR_NOMEM;
-    f->owner = ctx; f->device = ctx->device; f->pl = pl; f->pitch = align_up(pl.bytes, 256); f->d = nullptr;
-    for (size_t i = 0; i < ctx->frame_pool.size(); ++i)
-        if (ctx->frame_pool[i].pitch == f->pitch) {             // a destroyed frame's buffer of this size (its users have drained:
-            f->d = ctx->frame_pool[i].d;                        // every entry that takes a dsdtm_frame waits for its stream)
-            ctx->frame_pool.erase(ctx->frame_pool.begin() + (long)i);
-            *out = f;
-            return DSDTM_OK;
-        }
+    f->owner = ctx; f->device = ctx->device; f->pl = pl; f->pitch = align_up(pl.bytes, 256); f->d = pool_take(ctx, f->pitch);
+    if (f->d) { *out = f; return DSDTM_OK; }
     if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&f->d, f->pitch) != hipSuccess) {
         set_err(ctx, "hipMalloc of a %zu-byte frame failed", f->pitch);
         delete f;
@@ -1235,11 +1267,14 @@ extern "C" int dsdtm_frame_create_from_image(dsdtm_ctx* ctx, const uint8_t* leve
 
 extern "C" void dsdtm_frame_destroy(dsdtm_ctx* ctx, dsdtm_frame* f) {
     if (!f) return;
-    // its own, LIVE context: the buffer goes to that context's pool (no hipFree, which would wait for the whole device)
-    if (ctx && f->d && ctx_is_live(ctx) && f->owner == ctx && ctx->frame_pool.size() < dsdtm_ctx::FRAME_POOL) {
-        try { ctx->frame_pool.push_back(dsdtm_ctx::PooledFrame{f->pitch, f->d}); f->d = nullptr; } catch (...) {}
-        if (!f->d) { delete f; return; }
+    if (FrameSlab* sl = f->slab) {                                   // a frame of a batch: the slab goes with its last frame
+        delete f;
+        if (sl->refs.fetch_sub(1) != 1) return;
+        if (!pool_give(ctx, sl->owner, sl->device, sl->d, sl->bytes)) { (void)hipSetDevice(sl->device); if (sl->d) (void)hipFree(sl->d); }
+        delete sl;
+        return;
     }
+    if (pool_give(ctx, f->owner, f->device, f->d, f->pitch)) { delete f; return; }
     (void)hipSetDevice(f->device);
     if (f->d) (void)hipFree(f->d);       // hipFree waits for the device's pending work
     delete f;
@@ -1852,17 +1887,15 @@ extern "C" int dsdtm_pose_optimization(dsdtm_ctx* ctx, const double* bearing, co
     return DSDTM_OK;
 }
 
-// ---- one tracked frame in ONE submission (src/Tracking.cpp:199-256) ------------------------------
-// new frame -> Run -> ReprojectPoint + Get_ClosetObs for every local map point -> FindMatchDirect for all of them -> the cell
-// walk of SearchLocalPoints replayed on the device -> PoseOptimization, enqueued back to back on the context's stream; the host
-// waits once. What crosses the link crosses it once and off the kernels' critical paths: level 0 and Run's inputs are read from
-// host-mapped pinned memory by ONE kernel into HBM, the local map goes up on a second stream while Run runs, every later kernel
-// works on device memory and the few results are written (posted) to the pinned block by whichever kernel has them first.
-extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, dsdtm_track_result* res,
-                                 dsdtm_track_match* matches, double* residual_norm) {
-    if (!ctx) return DSDTM_ERR_INVALID;
-    if (!cam || !d || !res || !matches || !residual_norm) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
-    memset(res, 0, sizeof *res);
+// ---- the checks of a tracked frame's descriptor ------------------------------------------------------
+// The checks of a tracked frame's descriptor (dsdtm_track_frame, and every frame of dsdtm_track_frames): nothing is enqueued
+// or allocated before they pass.
+struct TrackPlan {
+    PackedPyr pl;
+    int st[DSDTM_MAX_LEVELS];
+    int nnz, max_search_level, grid_rows, grid_cols;
+};
+static int track_check_desc(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, TrackPlan* out) {
     if (!d->image || d->width <= 0 || d->height <= 0 || d->stride < d->width || d->levels <= 0 || d->levels > DSDTM_MAX_LEVELS ||
         d->width > 16384 || d->height > 16384) { set_err(ctx, "track: bad image geometry"); return DSDTM_ERR_INVALID; }
     // the grid, the packed mask (stride d->width) and the pyramid are sized by the image, the reprojection is bounded by the
@@ -1885,8 +1918,8 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
     const int max_search_level = d->max_pyr_levels - 3;                                      // src/Feature_alignment.cpp:144
     if (max_search_level < 0 || max_search_level >= d->levels) { set_err(ctx, "track: max_pyr_levels - 3 outside the pyramid"); return DSDTM_ERR_INVALID; }
     // the new frame's geometry (Frame::ComputeImagePyramid) must be the reference frame's and the keyframes'
-    PackedPyr pl;
-    int st[DSDTM_MAX_LEVELS];
+    PackedPyr& pl = out->pl;
+    int* st = out->st;
     pl.levels = d->levels;
     {
         size_t o = 0;
@@ -1906,6 +1939,7 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
     if (int rc = validate_params(ctx, &d->align, pl.levels)) return rc;
     const int M = d->n_points;
     const int nnz = M > 0 ? d->obs_offset[M] : 0;
+    out->nnz = nnz; out->max_search_level = max_search_level;
     if (M > 0) {
         if (d->obs_offset[0] != 0 || nnz < 0 || (nnz > 0 && (!d->obs_kf || !d->obs_px || !d->obs_level || !d->obs_bearing))) {
             set_err(ctx, "track: bad observation arrays"); return DSDTM_ERR_INVALID;
@@ -1922,7 +1956,27 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
     if ((long long)grid_rows * grid_cols > 4096) { set_err(ctx, "track: more than 4096 grid cells"); return DSDTM_ERR_INVALID; }
     const size_t lds = track_replay_lds_bytes(M, grid_rows * grid_cols, d->cell_size);
     if (lds > 160 * 1024 - 256) { set_err(ctx, "track: %d map points over %d cells do not fit one workgroup's LDS", M, grid_rows * grid_cols); return DSDTM_ERR_INVALID; }
+    out->grid_rows = grid_rows; out->grid_cols = grid_cols;
+    return DSDTM_OK;
+}
 
+// ---- one tracked frame in ONE submission (src/Tracking.cpp:199-256) ------------------------------
+// new frame -> Run -> ReprojectPoint + Get_ClosetObs for every local map point -> FindMatchDirect for all of them -> the cell
+// walk of SearchLocalPoints replayed on the device -> PoseOptimization, enqueued back to back on the context's stream; the host
+// waits once. What crosses the link crosses it once and off the kernels' critical paths: level 0 and Run's inputs are read from
+// host-mapped pinned memory by ONE kernel into HBM, the local map goes up on a second stream while Run runs, every later kernel
+// works on device memory and the few results are written (posted) to the pinned block by whichever kernel has them first.
+extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, dsdtm_track_result* res,
+                                 dsdtm_track_match* matches, double* residual_norm) {
+    if (!ctx) return DSDTM_ERR_INVALID;
+    if (!cam || !d || !res || !matches || !residual_norm) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
+    memset(res, 0, sizeof *res);
+    TrackPlan plan;
+    if (int rc = track_check_desc(ctx, cam, d, &plan)) return rc;
+    const PackedPyr& pl = plan.pl;
+    const int* st = plan.st;
+    const int max_search_level = plan.max_search_level, M = d->n_points, nnz = plan.nnz;
+    const int grid_rows = plan.grid_rows, grid_cols = plan.grid_cols;
     const size_t img = (size_t)d->width * d->height, nf = (size_t)d->n_ref_features, Mz = (size_t)M, NZ = (size_t)nnz,
                  MM = (size_t)d->max_matches, NK = (size_t)d->n_kf;
     // ---- the pinned block (host-mapped): inputs, then results ----
@@ -2155,6 +2209,399 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
         memcpy(&res->summary, h + h_sm, sizeof res->summary);
         if (res->n_matches > 0) memcpy(matches, h + h_match, (size_t)res->n_matches * sizeof(dsdtm_track_match));
         if (res->summary.n_residual_blocks > 0) memcpy(residual_norm, h + h_rn, (size_t)res->summary.n_residual_blocks * 8);
+    }
+    return DSDTM_OK;
+}
+
+// ---- n independent tracked frames in ONE submission ------------------------------------------------
+// dsdtm_track_frame for n frames of n independent trackers: every stage runs once for the whole batch — ingest of the n images
+// into ONE slab of packed pyramids (frame slot s at s * pitch) and the pyramid kernel over all of them; Run once per register
+// band present (the instantiation each frame's single call would run, its reference pyramid through a pointer table); the
+// reprojection + FindMatchDirect kernel over the columns of all frames (one frame per workgroup); the replay of the cell walk,
+// one workgroup per frame; the pose refinement, one instantiation per frame by its match count. The host waits once.
+// Inside the call frames sit in SLOT order — sorted by register band, so that each band's pairs are contiguous in the Run
+// arrays and in the slab — and are handed back in the caller's order.
+static int track_band(const dsdtm_track_desc* d) {
+    const bool run = d->n_ref_features >= d->align.min_fts && d->align.max_level - 1 >= d->align.min_level && d->n_ref_features > 0;
+    if (!run) return 7;                                            // no Run launch (the Min_fts rule, as the single call)
+    switch (sparse_align_pick_variant(d->n_ref_features)) {
+        case SA_REG128: return 0;
+        case SA_REG192: return 1;
+        case SA_REG256: return 2;
+        case SA_REG320: return 3;
+        case SA_REG448: return 4;
+        default: return 5;                                         // SA_REG704 (n_ref_features <= 704 is checked)
+    }
+}
+static const SAVariant kBandVariant[6] = {SA_REG128, SA_REG192, SA_REG256, SA_REG320, SA_REG448, SA_REG704};
+
+extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n_frames, const dsdtm_track_desc* descs,
+                                  dsdtm_track_result* results, dsdtm_track_match* matches, double* residual_norm, uint8_t* in_grid) {
+    if (!ctx) return DSDTM_ERR_INVALID;
+    if (n_frames < 0 || n_frames > DSDTM_TRACK_FRAMES_MAX) { set_err(ctx, "track_frames: n_frames %d outside 0..%d", n_frames, DSDTM_TRACK_FRAMES_MAX); return DSDTM_ERR_INVALID; }
+    if (n_frames == 0) return DSDTM_OK;
+    if (!cam || !descs || !results || !matches || !residual_norm) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
+    const int n = n_frames;
+    for (int f = 0; f < n; ++f) memset(&results[f], 0, sizeof results[f]);
+    // ---- every frame is checked before anything is allocated or enqueued ----
+    std::vector<TrackPlan> plans;
+    try { plans.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+    const dsdtm_track_desc& d0 = descs[0];
+    for (int f = 0; f < n; ++f) {
+        const dsdtm_track_desc* d = &descs[f];
+        const char* field = nullptr;
+        if (d->width != d0.width) field = "width";
+        else if (d->height != d0.height) field = "height";
+        else if (d->levels != d0.levels) field = "levels";
+        else if (d->align.max_level != d0.align.max_level || d->align.min_level != d0.align.min_level ||
+                 d->align.max_iters != d0.align.max_iters || d->align.min_fts != d0.align.min_fts) field = "align";
+        else if (d->min_tracked != d0.min_tracked) field = "min_tracked";
+        else if (d->cell_size != d0.cell_size) field = "cell_size";
+        else if (d->max_pyr_levels != d0.max_pyr_levels) field = "max_pyr_levels";
+        else if (d->max_matches != d0.max_matches) field = "max_matches";
+        else if (d->align2d_iters != d0.align2d_iters) field = "align2d_iters";
+        else if (d->pose_opt.max_iterations != d0.pose_opt.max_iterations) field = "pose_opt";
+        if (field) { set_err(ctx, "track_frames: frame %d: %s differs from frame 0 (shared across the batch)", f, field); return DSDTM_ERR_INVALID; }
+        if (int rc = track_check_desc(ctx, cam, d, &plans[(size_t)f])) {
+            char msg[sizeof ctx->err];
+            snprintf(msg, sizeof msg, "%s", ctx->err);
+            set_err(ctx, "track_frames: frame %d: %s", f, msg);
+            return rc;
+        }
+        if (d->n_ref_features > 704) { set_err(ctx, "track_frames: frame %d: %d reference features (at most 704)", f, d->n_ref_features); return DSDTM_ERR_INVALID; }
+        if (d->ref->pitch != align_up(plans[(size_t)f].pl.bytes, 256)) { set_err(ctx, "track_frames: frame %d: pyramid pitches differ", f); return DSDTM_ERR_INVALID; }
+    }
+    const TrackPlan& P = plans[0];
+    const PackedPyr& pl = P.pl;
+    const size_t pitch = align_up(pl.bytes, 256), img = (size_t)d0.width * d0.height, MM = (size_t)d0.max_matches;
+
+    // ---- slot order: by register band (stable) ----
+    std::vector<int> order, slot_of, band;
+    try { order.resize((size_t)n); slot_of.resize((size_t)n); band.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+    int band_lo[9] = {0};
+    for (int f = 0; f < n; ++f) { band[(size_t)f] = track_band(&descs[f]); band_lo[band[(size_t)f] + 1]++; }
+    for (int b = 0; b < 8; ++b) band_lo[b + 1] += band_lo[b];
+    {
+        int next[8];
+        for (int b = 0; b < 8; ++b) next[b] = band_lo[b];
+        for (int f = 0; f < n; ++f) { const int s = next[band[(size_t)f]]++; order[(size_t)s] = f; slot_of[(size_t)f] = s; }
+    }
+    // ---- sizes: columns (each frame padded to whole match workgroups, at least one), observations, keyframes, masks ----
+    size_t MF = 1, C = 0, NZ = 0, NK = 0, NMASK = 0;
+    int max_points = 0;
+    std::vector<int32_t> col0, blk_frame;
+    try { col0.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+    for (int s = 0; s < n; ++s) {
+        const dsdtm_track_desc* d = &descs[order[(size_t)s]];
+        if ((size_t)d->n_ref_features > MF) MF = (size_t)d->n_ref_features;
+        col0[(size_t)s] = (int32_t)C;
+        const size_t groups = d->n_points > 0 ? ((size_t)d->n_points + TRACK_COL_GROUP - 1) / TRACK_COL_GROUP : 1;
+        try { for (size_t g = 0; g < groups; ++g) blk_frame.push_back(s); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+        C += groups * TRACK_COL_GROUP;
+        NZ += (size_t)plans[(size_t)order[(size_t)s]].nnz;
+        NK += (size_t)d->n_kf;
+        if (d->mask) NMASK++;
+        if (d->n_points > max_points) max_points = d->n_points;
+    }
+    const size_t NF = (size_t)n, NB = blk_frame.size();
+
+    // ---- the pinned block (host-mapped) ----
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
+    // Run's range (slot order, features at stride MF): inputs, then the poses / counts / statistics Run writes
+    const size_t h_run = o;
+    const size_t h_px = take(NF * MF * 8), h_bear = take(NF * MF * 24), h_pw = take(NF * MF * 24), h_ini = take(NF * MF),
+                 h_nf = take(NF * 4), h_tr = take(NF * 96), h_rp = take(NF * sizeof(void*));
+    const size_t h_T = take(NF * 96), h_nt = take(NF * 4), h_st = take(NF * sizeof(dsdtm_align_stats));
+    const size_t run_bytes = o - h_run, run_out_bytes = o - h_T;
+    // the local maps and masks (slot order, columns padded): one range, copied up in one piece
+    const size_t h_map = o;
+    const size_t h_mask = take(NMASK * img), h_fmask = take(NF * sizeof(void*)), h_bf = take(NB * 4), h_c0 = take(NF * 4),
+                 h_np = take(NF * 4), h_mpw = take(C * 24), h_found = take(C * 4), h_bad = take(C), h_off = take((C + 1) * 4),
+                 h_okf = take(NZ * 4), h_opx = take(NZ * 8), h_olv = take(NZ * 4), h_ob = take(NZ * 24), h_Tkf = take(NK * 96),
+                 h_kfp = take(NK * sizeof(void*));
+    const size_t map_bytes = o - h_map;
+    // results the kernels post straight into the pinned block
+    const size_t h_cnt = take(NF * 16), h_match = take(NF * MM * sizeof(dsdtm_track_match)), h_Topt = take(NF * 96),
+                 h_sm = take(NF * sizeof(dsdtm_pose_opt_summary)), h_rn = take(NF * MM * 8), h_grid = take(C);
+    // pageable host images are staged here
+    size_t n_staged = 0;
+    std::vector<uint8_t> kind;   // 0: staged, 1: pinned (host-mapped), 2: device, 3: device through the copy engine, 4: pinned through the copy engine
+    std::vector<const void*> src;
+    try { kind.resize(NF); src.resize(NF); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+    for (int f = 0; f < n; ++f) {
+        const dsdtm_track_desc* d = &descs[f];
+        bool pinned_image = false, device_image = false;
+        hipPointerAttribute_t pa_;
+        if (hipPointerGetAttributes(&pa_, d->image) == hipSuccess) {
+            device_image = pa_.type == hipMemoryTypeDevice;
+            pinned_image = pa_.type == hipMemoryTypeHost && d->stride == d->width;
+            if (device_image && pa_.device != ctx->device) { set_err(ctx, "track_frames: frame %d: the image lives on device %d, the context on %d", f, pa_.device, ctx->device); return DSDTM_ERR_INVALID; }
+        } else (void)hipGetLastError();
+        kind[(size_t)f] = 0; src[(size_t)f] = nullptr;
+        if (device_image) {
+            kind[(size_t)f] = (d->stride == d->width && !(((size_t)d->image) & 15)) ? 2 : 3;
+            src[(size_t)f] = d->image;
+        } else if (pinned_image) {
+            void* p_ = nullptr;
+            if (!(((size_t)d->image) & 15) && hipHostGetDevicePointer(&p_, (void*)d->image, 0) == hipSuccess) { kind[(size_t)f] = 1; src[(size_t)f] = p_; }
+            else { (void)hipGetLastError(); kind[(size_t)f] = 4; src[(size_t)f] = d->image; }
+        } else n_staged++;
+    }
+    const size_t img_pitch = align_up(img, 256);             // (ingest_kernel reads 16-byte aligned sources)
+    const size_t h_img = take(n_staged * img_pitch);
+    const size_t h_total = o;
+    // ---- device scratch ----
+    o = 0;
+    const size_t g_run = take(run_bytes), g_map = take(map_bytes), g_pw = take(C * 24), g_cell = take(C * 4), g_px0 = take(C * 16),
+                 g_px = take(C * 16), g_ck = take(C * 4), g_cf = take(C * 4), g_rpx = take(C * 8), g_rl = take(C * 4), g_rb = take(C * 24),
+                 g_ib = take(C), g_sl = take(C * 4), g_cv = take(C), g_grid = take(C), g_pob = take(NF * MM * 24),
+                 g_pow = take(NF * MM * 24), g_pol = take(NF * MM * 4), g_pou = take(NF * MM), g_pon = take(NF * 4), g_Topt = take(NF * 96);
+    const size_t g_total = o;
+    if (int rc = ensure_stage(ctx, h_total > g_total ? h_total : g_total)) return rc;
+    uint8_t* h = (uint8_t*)ctx->h_pinned;
+    uint8_t* g = (uint8_t*)ctx->d_stage;
+    void* hd_ = nullptr;
+    HIP_TRY(ctx, hipHostGetDevicePointer(&hd_, ctx->h_pinned, 0));
+    uint8_t* hd = (uint8_t*)hd_;
+    hipStream_t stream = ctx->stream;
+    uint8_t* const gr = g + g_run - h_run;      // device address of pinned offset X inside Run's range: gr + X
+    uint8_t* const gm = g + g_map - h_map;      // ... inside the map range: gm + X
+
+    // ---- the slab ----
+    const size_t slab_bytes = pitch * NF;
+    uint8_t* slab = pool_take(ctx, slab_bytes);
+    if (!slab && (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&slab, slab_bytes) != hipSuccess)) {
+        (void)hipGetLastError();
+        set_err(ctx, "hipMalloc of a %zu-byte slab of %d frames failed", slab_bytes, n);
+        return DSDTM_ERR_NOMEM;
+    }
+    auto fail = [&](int rc) {
+        if (ctx->copy_stream[0]) (void)hipStreamSynchronize(ctx->copy_stream[0]);
+        (void)hipStreamSynchronize(stream);
+        if (!pool_give(ctx, ctx, ctx->device, slab, slab_bytes)) (void)hipFree(slab);
+        return rc;
+    };
+#define TRACKS_TRY(call)                                                                                       \
+    do {                                                                                                       \
+        hipError_t e_ = (call);                                                                                \
+        if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
+    } while (0)
+
+    // ---- 1. Run's range: features, poses seeded (src/Tracking.cpp:201), counts and statistics cleared ----
+    for (int s = 0; s < n; ++s) {
+        const dsdtm_track_desc* d = &descs[order[(size_t)s]];
+        const size_t nf = (size_t)d->n_ref_features, S = (size_t)s;
+        if (nf) {
+            memcpy(h + h_px + S * MF * 8, d->ref_px_xy, nf * 8);
+            memcpy(h + h_bear + S * MF * 24, d->ref_bearing, nf * 24);
+            memcpy(h + h_pw + S * MF * 24, d->ref_p_world, nf * 24);
+            memcpy(h + h_ini + S * MF, d->ref_initial, nf);
+        }
+        ((int32_t*)(h + h_nf))[s] = (int32_t)nf;
+        memcpy(h + h_tr + S * 96, d->T_ref_w, 96);
+        ((const uint8_t**)(h + h_rp))[s] = d->ref->d;
+        memcpy(h + h_T + S * 96, d->T_seed, 96);
+    }
+    memset(h + h_nt, 0, NF * 4);
+    memset(h + h_st, 0, NF * sizeof(dsdtm_align_stats));
+    // ---- 2. the new frames: level 0 of each into its slot of the slab (the first ingest also moves Run's range), the pyramids ----
+    {
+        size_t staged = 0;
+        bool run_moved = false;
+        for (int s = 0; s < n; ++s) {
+            const int f = order[(size_t)s];
+            const dsdtm_track_desc* d = &descs[f];
+            uint8_t* dst = slab + (size_t)s * pitch;
+            const void* from = src[(size_t)f];
+            const uint8_t k = kind[(size_t)f];
+            if (k == 0) {
+                uint8_t* hs = h + h_img + staged * img_pitch;
+                if (d->stride == d->width) memcpy(hs, d->image, img);
+                else for (int y = 0; y < d->height; ++y) memcpy(hs + (size_t)y * d->width, d->image + (size_t)y * d->stride, (size_t)d->width);
+                from = hd + h_img + staged * img_pitch;
+                staged++;
+            }
+            const void* r_src = run_moved ? nullptr : (const void*)(hd + h_run);
+            void* r_dst = run_moved ? nullptr : (void*)(g + g_run);
+            const size_t r_bytes = run_moved ? 0 : run_bytes;
+            if (k == 3) TRACKS_TRY(hipMemcpy2DAsync(dst, (size_t)d->width, d->image, (size_t)d->stride, (size_t)d->width, (size_t)d->height, hipMemcpyDeviceToDevice, stream));
+            else if (k == 4) TRACKS_TRY(hipMemcpyAsync(dst, d->image, img, hipMemcpyHostToDevice, stream));
+            if (k == 3 || k == 4) { if (!run_moved) TRACKS_TRY(ingest_launch(nullptr, nullptr, 0, r_src, r_dst, r_bytes, stream)); }
+            else TRACKS_TRY(ingest_launch(from, dst, img, r_src, r_dst, r_bytes, stream));
+            run_moved = true;
+        }
+    }
+    if (int rc = dsdtm_pyrdown_batch_device(ctx, slab, pitch, n, pl.levels, pl.w, pl.h, P.st, pl.off, stream)) return fail(rc);
+
+    // ---- 3. Run: one launch per register band present, one-CU kernels, reference pyramids through the pointer table ----
+    volatile unsigned* h_flag = ctx->h_flags + dsdtm_ctx::FLAG_SINGLE;
+    *h_flag = 0;
+    for (int b = 0; b < 6; ++b) {
+        const int lo = band_lo[b], cnt = band_lo[b + 1] - band_lo[b];
+        if (cnt <= 0) continue;
+        const size_t L = (size_t)lo;
+        dsdtm_batch_desc bd;
+        memset(&bd, 0, sizeof bd);
+        bd.n_pairs = cnt; bd.max_features = (int)MF; bd.levels = pl.levels;
+        for (int l = 0; l < pl.levels; ++l) { bd.width[l] = pl.w[l]; bd.height[l] = pl.h[l]; bd.stride[l] = pl.w[l]; bd.level_offset[l] = pl.off[l]; }
+        bd.pyr_pitch = pitch;
+        bd.ref_pyr = slab + L * pitch;                            // (not read by the pointer-table kernel: a range of the right size)
+        bd.cur_pyr = slab + L * pitch;
+        bd.px_xy = (const float*)(gr + h_px) + L * MF * 2; bd.bearing = (const double*)(gr + h_bear) + L * MF * 3;
+        bd.p_world = (const double*)(gr + h_pw) + L * MF * 3; bd.initial = gr + h_ini + L * MF;
+        bd.n_features = (const int32_t*)(gr + h_nf) + L;
+        bd.T_ref_w = (const double*)(gr + h_tr) + L * 12; bd.T_cur_w = (double*)(gr + h_T) + L * 12;
+        bd.n_tracked = (int32_t*)(gr + h_nt) + L; bd.stats = (dsdtm_align_stats*)(gr + h_st) + L;
+        LaunchMode mode;
+        mode.single = true; mode.one_cu = true; mode.variant = (int)kBandVariant[b];
+        mode.ref_ptrs = (const uint8_t* const*)(gr + h_rp) + L;
+        if (int rc = launch_batch(ctx, &bd, cam, &d0.align, stream, mode, nullptr)) return fail(rc);
+    }
+
+    // ---- 4. the local maps: packed in slot order (observations name keyframes in the concatenated table), copied up on a
+    //         second stream while Run runs ----
+    {
+        size_t cz = 0, z = 0, kb = 0, mk = 0;
+        int32_t* off = (int32_t*)(h + h_off);
+        for (int s = 0; s < n; ++s) {
+            const int f = order[(size_t)s];
+            const dsdtm_track_desc* d = &descs[f];
+            const size_t M = (size_t)d->n_points, c0 = (size_t)col0[(size_t)s], nnz = (size_t)plans[(size_t)f].nnz;
+            const size_t cols = (s + 1 < n ? (size_t)col0[(size_t)s + 1] : C) - c0;
+            ((int32_t*)(h + h_c0))[s] = (int32_t)c0;
+            ((int32_t*)(h + h_np))[s] = (int32_t)M;
+            if (d->mask) {
+                for (int y = 0; y < d->height; ++y) memcpy(h + h_mask + mk * img + (size_t)y * d->width, d->mask + (size_t)y * d->mask_stride, (size_t)d->width);
+                ((const uint8_t**)(h + h_fmask))[s] = gm + h_mask + mk * img;
+                mk++;
+            } else ((const uint8_t**)(h + h_fmask))[s] = nullptr;
+            if (M) {
+                memcpy(h + h_mpw + c0 * 24, d->mp_world, M * 24);
+                memcpy(h + h_found + c0 * 4, d->mp_found, M * 4);
+                memcpy(h + h_bad + c0, d->mp_bad, M);
+            }
+            for (size_t i = 0; i < cols; ++i) off[c0 + i] = (int32_t)(z + (i < M ? (size_t)d->obs_offset[i] : nnz));
+            if (nnz) {
+                for (size_t j = 0; j < nnz; ++j) ((int32_t*)(h + h_okf))[z + j] = d->obs_kf[j] + (int32_t)kb;
+                memcpy(h + h_opx + z * 8, d->obs_px, nnz * 8);
+                memcpy(h + h_olv + z * 4, d->obs_level, nnz * 4);
+                memcpy(h + h_ob + z * 24, d->obs_bearing, nnz * 24);
+            }
+            if (d->n_kf > 0) memcpy(h + h_Tkf + kb * 96, d->T_kf_w, (size_t)d->n_kf * 96);
+            for (int k = 0; k < d->n_kf; ++k) ((const uint8_t**)(h + h_kfp))[kb + (size_t)k] = d->kf[k]->d;
+            cz += cols; z += nnz; kb += (size_t)d->n_kf;
+        }
+        off[C] = (int32_t)z;
+        memcpy(h + h_bf, blk_frame.data(), NB * 4);
+        if (!ctx->copy_stream[0]) TRACKS_TRY(hipStreamCreateWithFlags(&ctx->copy_stream[0], hipStreamNonBlocking));
+        TRACKS_TRY(hipMemcpyAsync(g + g_map, h + h_map, map_bytes, hipMemcpyHostToDevice, ctx->copy_stream[0]));
+        TRACKS_TRY(hipStreamSynchronize(ctx->copy_stream[0]));
+    }
+
+    // ---- 5. reprojection + FindMatchDirect over all columns; the replays; the refinements ----
+    TrackArgs t;
+    memset(&t, 0, sizeof t);
+    t.T_run = (const double*)(gr + h_T); t.n_tracked = (const int32_t*)(gr + h_nt); t.min_tracked = d0.min_tracked;
+    t.run_out_dev = gr + h_T; t.run_out_host = hd + h_T; t.run_out_n16 = 0;     // (Run's results come back by one copy, below)
+    t.T_kf_w = (const double*)(gm + h_Tkf); t.kf_ptrs = (const uint8_t* const*)(gm + h_kfp); t.n_kf = (int)NK;
+    t.mp_world = (const double*)(gm + h_mpw); t.mp_found = (const int32_t*)(gm + h_found); t.mp_bad = gm + h_bad; t.n_points = (int)C;
+    t.obs_offset = (const int32_t*)(gm + h_off); t.obs_kf = (const int32_t*)(gm + h_okf); t.obs_px = (const float*)(gm + h_opx);
+    t.obs_level = (const int32_t*)(gm + h_olv); t.obs_bearing = (const double*)(gm + h_ob);
+    t.mask = nullptr; t.mask_stride = d0.width;
+    t.fx = cam->fx; t.fy = cam->fy; t.cx = cam->cx; t.cy = cam->cy; t.width = cam->width; t.height = cam->height; t.levels = pl.levels;
+    t.cell_size = d0.cell_size; t.grid_cols = P.grid_cols; t.grid_rows = P.grid_rows; t.max_matches = d0.max_matches;
+    track_disc_half_widths(d0.cell_size, t.disc_hw);
+    t.pw = (double*)(g + g_pw); t.cell = (int32_t*)(g + g_cell); t.px0 = (double*)(g + g_px0); t.px = (double*)(g + g_px);
+    t.cand_kf = (int32_t*)(g + g_ck); t.cand_frame = (int32_t*)(g + g_cf); t.ref_px = (float*)(g + g_rpx); t.ref_level = (int32_t*)(g + g_rl);
+    t.ref_bearing = (double*)(g + g_rb); t.init_blocked = g + g_ib; t.search_level = (int32_t*)(g + g_sl); t.converged = g + g_cv;
+    t.matches = (dsdtm_track_match*)(hd + h_match); t.counts = (int32_t*)(hd + h_cnt); t.T_opt = (double*)(g + g_Topt);
+    t.po_bearing = (double*)(g + g_pob); t.po_world = (double*)(g + g_pow); t.po_level = (int32_t*)(g + g_pol); t.po_use = g + g_pou;
+    t.po_n = (int32_t*)(g + g_pon);
+    t.n_frames = n; t.blk_frame = (const int32_t*)(gm + h_bf); t.f_col0 = (const int32_t*)(gm + h_c0); t.f_np = (const int32_t*)(gm + h_np);
+    t.f_mask = (const uint8_t* const*)(gm + h_fmask); t.in_grid = g + g_grid; t.max_points = max_points;
+
+    WarpKernelArgs wa;
+    memset(&wa, 0, sizeof wa);
+    for (int l = 0; l < pl.levels; ++l) { wa.lv[l].w = pl.w[l]; wa.lv[l].h = pl.h[l]; wa.lv[l].stride = pl.w[l]; wa.lv[l].off = (uint32_t)pl.off[l]; }
+    wa.kf_ptrs = t.kf_ptrs; wa.T_kf_w = t.T_kf_w; wa.T_cur_w_arr = t.T_run; wa.cand_frame = t.cand_frame;
+    wa.cand_kf = t.cand_kf; wa.ref_px = t.ref_px; wa.ref_level = t.ref_level; wa.ref_bearing = t.ref_bearing; wa.p_world = t.pw;
+    wa.search_level = t.search_level; wa.m = (int)C; wa.n_kf = (int)NK; wa.max_search_level = P.max_search_level; wa.levels = pl.levels;
+    wa.n_frames = n; wa.fx = cam->fx; wa.fy = cam->fy; wa.cx = cam->cx; wa.cy = cam->cy; wa.no_xcd = options().fmd_no_xcd;
+    A2DKernelArgs aa;
+    memset(&aa, 0, sizeof aa);
+    aa.cur_pyr = slab; aa.level = t.search_level; aa.px_xy = t.px; aa.converged = t.converged; aa.m = (int)C; aa.max_iters = d0.align2d_iters;
+    aa.levels = pl.levels; aa.px_level0 = 1; aa.frame = t.cand_frame; aa.n_frames = n; aa.pyr_pitch = pitch;
+    for (int l = 0; l < pl.levels; ++l) aa.lv[l] = wa.lv[l];
+
+    PoseOptArgs pa;
+    pa.n_frames = n; pa.max_features = d0.max_matches; pa.max_iterations = d0.pose_opt.max_iterations;
+    pa.n_features = t.po_n; pa.bearing = t.po_bearing; pa.p_world = t.po_world; pa.level = t.po_level; pa.use = t.po_use;
+    pa.T_cur_w = t.T_opt; pa.T_mirror = (double*)(hd + h_Topt); pa.residual_norm = (double*)(hd + h_rn); pa.summary = (dsdtm_pose_opt_summary*)(hd + h_sm);
+    pa.force_variant = 3;                                          // one wave / four waves per frame by its match count, as the single call
+
+    memset(h + h_cnt, 0, NF * 16); memset(h + h_sm, 0, NF * sizeof(dsdtm_pose_opt_summary));
+    TRACKS_TRY(track_match_launch(t, wa, aa, stream));
+    TRACKS_TRY(track_replay_launch(t, stream));
+    TRACKS_TRY(pose_opt_launch(pa, stream));
+    TRACKS_TRY(hipMemcpyAsync(h + h_T, g + g_run + (h_T - h_run), run_out_bytes, hipMemcpyDeviceToHost, stream));
+    if (in_grid) TRACKS_TRY(hipMemcpyAsync(h + h_grid, g + g_grid, C, hipMemcpyDeviceToHost, stream));
+    TRACKS_TRY(hipStreamSynchronize(stream));
+    if (*h_flag) {
+        *h_flag = 0;
+        for (int i = 0; i < dsdtm_ctx::MAX_STREAMS; ++i)
+            if (ctx->rings[i].used && ctx->rings[i].stream == ctx->stream)
+                (void)hipMemset(ctx->d_counter + i * dsdtm_ctx::COUNTERS_PER_STREAM, 0, sizeof(unsigned) * dsdtm_ctx::COUNTERS_PER_STREAM);
+        set_err(ctx, "sparse-align kernel: intra-workgroup hand-over timed out");
+        return fail(DSDTM_ERR_HIP);
+    }
+    const int32_t* cnt = (const int32_t*)(h + h_cnt);
+    for (int s = 0; s < n; ++s) {
+        const bool lost = ((const int32_t*)(h + h_nt))[s] < d0.min_tracked;
+        if (cnt[4 * s + 2] == 2 && !lost) { set_err(ctx, "track_frames: frame %d: the replay of the cell walk did not settle", order[(size_t)s]); return fail(DSDTM_ERR_HIP); }
+    }
+#undef TRACKS_TRY
+    // ---- the frames (all or nothing) ----
+    FrameSlab* sl = new (std::nothrow) FrameSlab();
+    std::vector<dsdtm_frame*> fr;
+    bool ok = sl != nullptr;
+    if (ok) { try { fr.assign(NF, nullptr); } catch (...) { ok = false; } }
+    for (int s = 0; ok && s < n; ++s) {
+        dsdtm_frame* f = new (std::nothrow) dsdtm_frame();
+        if (!f) { ok = false; break; }
+        f->owner = ctx; f->device = ctx->device; f->d = slab + (size_t)s * pitch; f->pitch = pitch; f->pl = pl; f->slab = sl;
+        fr[(size_t)s] = f;
+    }
+    if (!ok) {
+        for (dsdtm_frame* f : fr) delete f;
+        delete sl;
+        set_err(ctx, "out of host memory");
+        return fail(DSDTM_ERR_NOMEM);
+    }
+    sl->owner = ctx; sl->device = ctx->device; sl->d = slab; sl->bytes = slab_bytes; sl->refs.store(n);
+    size_t grid_at = 0;
+    std::vector<size_t> grid_start(NF, 0);
+    for (int f = 0; f < n; ++f) { grid_start[(size_t)f] = grid_at; grid_at += (size_t)descs[f].n_points; }
+    for (int s = 0; s < n; ++s) {
+        const int f = order[(size_t)s];
+        const size_t S = (size_t)s;
+        dsdtm_track_result* res = &results[f];
+        res->frame = fr[S];
+        memcpy(res->T_run, h + h_T + S * 96, 96);
+        res->n_tracked = ((const int32_t*)(h + h_nt))[s];
+        memcpy(&res->stats, h + h_st + S * sizeof(dsdtm_align_stats), sizeof res->stats);
+        res->lost = res->n_tracked < d0.min_tracked ? 1 : 0;
+        res->n_in_grid = cnt[4 * s];
+        res->n_matches = res->lost ? 0 : cnt[4 * s + 1];
+        res->replay_full_scan = cnt[4 * s + 2] == 1 ? 1 : 0;
+        if (res->lost) memcpy(res->T_opt, res->T_run, 96);
+        else {
+            memcpy(res->T_opt, h + h_Topt + S * 96, 96);
+            memcpy(&res->summary, h + h_sm + S * sizeof(dsdtm_pose_opt_summary), sizeof res->summary);
+            if (res->n_matches > 0) memcpy(matches + (size_t)f * MM, h + h_match + S * MM * sizeof(dsdtm_track_match), (size_t)res->n_matches * sizeof(dsdtm_track_match));
+            if (res->summary.n_residual_blocks > 0) memcpy(residual_norm + (size_t)f * MM, h + h_rn + S * MM * 8, (size_t)res->summary.n_residual_blocks * 8);
+        }
+        if (in_grid && descs[f].n_points > 0) memcpy(in_grid + grid_start[(size_t)f], h + h_grid + (size_t)col0[S], (size_t)descs[f].n_points);
     }
     return DSDTM_OK;
 }

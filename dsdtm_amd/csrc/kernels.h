@@ -39,6 +39,9 @@ struct SAKernelArgs {
     int max_level, min_level, max_iters, min_fts;
     float fx, fy, cx, cy, f;
     LevelGeom lv[DSDTM_MAX_LEVELS];
+    // dsdtm_track_frames: pair p's reference pyramid is ref_ptrs[p] (device array of separately allocated pyramids, each
+    // pyr_pitch bytes) instead of ref_pyr + p * pyr_pitch; null: the packed layout. Register kernels only.
+    const uint8_t* const* ref_ptrs;
 };
 
 // Diagnostic switches (A/B runs, tests). They exist as VARIABLES only in the diagnostic build (build.py --diag,
@@ -213,10 +216,22 @@ struct TrackArgs {
     dsdtm_track_match* matches; int32_t* counts;      // counts: [0] points in the grid, [1] matches, [2] 1 = the full scan ran
     double* T_opt;                                    // device: the pose refinement's in/out pose, seeded with T_run
     double* po_bearing; double* po_world; int32_t* po_level; uint8_t* po_use; int32_t* po_n;
+    // dsdtm_track_frames (n_frames > 0: n independent frames; 0: one frame, the fields below unused). The columns above hold the
+    // frames back to back, each padded to whole workgroups of the match kernel: frame f owns columns f_col0[f] ..
+    // f_col0[f] + f_np[f] - 1 and the match kernel's workgroups from f_col0[f] / MATCH_G (blk_frame: the frame of every
+    // workgroup, at least one per frame). n_points = all columns, n_kf = all keyframes (observations name them globally).
+    // Per frame f: Run's pose / count at T_run + 12 f / n_tracked + f, its mask f_mask[f] (stride mask_stride, null = none),
+    // matches and refinement columns from f * max_matches, counts + 4 f, po_n + f, T_opt + 12 f.
+    int n_frames;
+    const int32_t* blk_frame; const int32_t* f_col0; const int32_t* f_np; const uint8_t* const* f_mask;
+    uint8_t* in_grid;                                 // per column: 1 = ReprojectPoint put the point into the grid
+    int max_points;                                   // the largest f_np (the replay's LDS and elements per thread)
 };
+constexpr int TRACK_COL_GROUP = 16;   // candidates per workgroup of the track match kernels (MATCH_G of match_body.h)
 // reprojection of every local map point + FindMatchDirect for it (wa / aa: the fused FindMatchDirect kernel's arguments over the
 // candidate columns of `args`)
 hipError_t track_match_launch(const TrackArgs& args, const WarpKernelArgs& wa, const A2DKernelArgs& aa, hipStream_t stream);
+// (with args.n_frames > 0 both launch the batch kernels: one frame per workgroup range / per replay workgroup)
 hipError_t track_replay_launch(const TrackArgs& args, hipStream_t stream);
 size_t track_replay_lds_bytes(int n_points, int n_cells, int radius);
 void track_disc_half_widths(int radius, int8_t* hw);   // radius <= 127

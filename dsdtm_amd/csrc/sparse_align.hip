@@ -1079,8 +1079,10 @@ struct RegSmem {
     uint32_t win[PPW][WIN_ROWS * 3 * NPW * 64];          // current-image footprint windows (residual_patch), [plane][lane]
 };
 
-template <int NPW, int PPW, bool STAMPS = false>
-__global__ __launch_bounds__(PPW * (NPW + 1) * 64) void sparse_align_reg_kernel(const SAKernelArgs a) {
+// The register kernel's body. PTRS: pair p's reference pyramid is a.ref_ptrs[p] (dsdtm_track_frames: the reference frames are
+// separate allocations) — a kernel of its own (sparse_align_reg_ptrs_kernel), so the packed-layout instantiations keep their code.
+template <int NPW, int PPW, bool STAMPS, bool PTRS>
+__device__ __forceinline__ void sparse_align_reg_body(const SAKernelArgs a) {
     constexpr int NP = NPW * 4;            // one partial slot per 16-lane DPP row
     constexpr int WPP = NPW + 1;           // waves per pair
     __shared__ RegSmem<NPW, PPW> sm;
@@ -1246,7 +1248,7 @@ __global__ __launch_bounds__(PPW * (NPW + 1) * 64) void sparse_align_reg_kernel(
             continue;
         }
         const int nf = a.n_features ? a.n_features[pair] : a.max_features;
-        const uint8_t* __restrict__ ref_base = a.ref_pyr + (size_t)pair * a.pyr_pitch;
+        const uint8_t* __restrict__ ref_base = PTRS ? a.ref_ptrs[pair] : a.ref_pyr + (size_t)pair * a.pyr_pitch;
         const uint8_t* __restrict__ cur_base = a.cur_pyr + (size_t)pair * a.pyr_pitch;
         const FeatureRaw fraw = load_feature_raw(a, (size_t)pair * a.max_features + ltid, ltid < nf);
         unsigned long long st_pre = 0, st_pass = 0, st_h = 0, st_bar = 0;
@@ -1374,6 +1376,17 @@ __global__ __launch_bounds__(PPW * (NPW + 1) * 64) void sparse_align_reg_kernel(
             for (int l = 0; l < 8; ++l) o[4 + l] = st_lvl[l];
         }
     }
+}
+
+template <int NPW, int PPW, bool STAMPS = false>
+__global__ __launch_bounds__(PPW * (NPW + 1) * 64) void sparse_align_reg_kernel(const SAKernelArgs a) {
+    sparse_align_reg_body<NPW, PPW, STAMPS, false>(a);
+}
+
+// dsdtm_track_frames: Run for n pairs whose reference frames are separate allocations (a.ref_ptrs)
+template <int NPW, int PPW>
+__global__ __launch_bounds__(PPW * (NPW + 1) * 64) void sparse_align_reg_ptrs_kernel(const SAKernelArgs a) {
+    sparse_align_reg_body<NPW, PPW, false, true>(a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2161,8 +2174,12 @@ static unsigned persistent_grid(int n_pairs, int ppw, int num_cus) {
 template <int NPW, int PPW, bool STAMPS>
 static hipError_t launch_reg(const SAKernelArgs& args, int num_cus, hipStream_t stream) {
     static_assert(sizeof(RegSmem<NPW, PPW>) <= 64 * 1024, "static LDS");
-    hipLaunchKernelGGL((sparse_align_reg_kernel<NPW, PPW, STAMPS>), dim3(persistent_grid(args.n_pairs, PPW, num_cus)),
-                       dim3(PPW * (NPW + 1) * 64), 0, stream, args);
+    if (!STAMPS && args.ref_ptrs)
+        hipLaunchKernelGGL((sparse_align_reg_ptrs_kernel<NPW, PPW>), dim3(persistent_grid(args.n_pairs, PPW, num_cus)),
+                           dim3(PPW * (NPW + 1) * 64), 0, stream, args);
+    else
+        hipLaunchKernelGGL((sparse_align_reg_kernel<NPW, PPW, STAMPS>), dim3(persistent_grid(args.n_pairs, PPW, num_cus)),
+                           dim3(PPW * (NPW + 1) * 64), 0, stream, args);
     return hipGetLastError();
 }
 
@@ -2211,6 +2228,7 @@ hipError_t sparse_align_launch(const SAKernelArgs& args, SAVariant variant, int 
         case SA_REG448: return launch_reg<7, 1, false>(args, num_cus, stream);
         case SA_REG704: return launch_reg<11, 1, false>(args, num_cus, stream);
         case SA_WS: {
+            if (args.ref_ptrs) return hipErrorInvalidValue;              // (register kernels only: <= 704 features)
             const int npad = (args.max_features + 63) / 64 * 64;
             const bool ws_windows = !options().ws_no_windows;
             const dim3 grid((unsigned)args.n_pairs);

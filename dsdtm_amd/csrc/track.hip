@@ -55,8 +55,11 @@ __device__ __forceinline__ void camera_centre(const double* __restrict__ m, doub
 }  // namespace
 
 // ReprojectPoint + Get_ClosetObs + the reference-pixel test for map point i with the pose m (3x4, LDS): writes the
-// candidate columns of point i (thread = map point)
-__device__ __forceinline__ void reproject_point(const TrackArgs& a, int i, const double* m, bool lost) {
+// candidate columns of point i (thread = map point). BATCH (dsdtm_track_frames): column i belongs to frame `frame`, whose mask
+// is `mask`; the in-grid flag goes out too.
+template <bool BATCH = false>
+__device__ __forceinline__ void reproject_point(const TrackArgs& a, int i, const double* m, bool lost, int frame = 0,
+                                                const uint8_t* mask = nullptr) {
     const double P0 = a.mp_world[3 * (size_t)i], P1 = a.mp_world[3 * (size_t)i + 1], P2 = a.mp_world[3 * (size_t)i + 2];
     const bool bad = a.mp_bad[i] != 0;                             // UpdateLocalMap skips bad points (src/Tracking.cpp:288)
     const int o_lo = a.obs_offset[i], o_hi = a.obs_offset[i + 1];
@@ -101,7 +104,8 @@ __device__ __forceinline__ void reproject_point(const TrackArgs& a, int i, const
     a.px0[2 * (size_t)i] = u; a.px0[2 * (size_t)i + 1] = v;
     a.px[2 * (size_t)i] = u; a.px[2 * (size_t)i + 1] = v;          // in/out of FindMatchDirect
     a.cand_kf[i] = best;                                           // -1: rejected by FindMatchDirect (search level -1, not converged)
-    a.cand_frame[i] = 0;
+    a.cand_frame[i] = BATCH ? frame : 0;
+    if constexpr (BATCH) a.in_grid[i] = in_grid ? 1 : 0;
     if (jbest >= 0) {
         a.ref_px[2 * (size_t)i] = a.obs_px[2 * (size_t)jbest]; a.ref_px[2 * (size_t)i + 1] = a.obs_px[2 * (size_t)jbest + 1];
         a.ref_level[i] = a.obs_level[jbest];
@@ -115,7 +119,8 @@ __device__ __forceinline__ void reproject_point(const TrackArgs& a, int i, const
     // the mask test of ReprojectCell (:96) reads the reprojected pixel narrowed to cv::Point2f and rounded; the caller's mask
     // at the start of the search
     uint8_t blocked = 0;
-    if (in_grid && a.mask) blocked = a.mask[(size_t)cv_round(v) * a.mask_stride + cv_round(u)] != 255 ? 1 : 0;
+    const uint8_t* const mk = BATCH ? mask : a.mask;
+    if (in_grid && mk) blocked = mk[(size_t)cv_round(v) * a.mask_stride + cv_round(u)] != 255 ? 1 : 0;
     a.init_blocked[i] = blocked;
 }
 
@@ -145,6 +150,40 @@ __global__ __launch_bounds__(256) void track_match_kernel(const TrackArgs t, con
         reproject_point(t, cb + tid, s_T, s_lost != 0);
         sh.c[tid] = warp_candidate(a, cb + tid);
         sh.sl[tid] = a.search_level[cb + tid];                     // written by warp_candidate (this thread)
+    }
+    __syncthreads();
+    match_rounds<MATCH_G>(a, b, sh, cb, nb, tid);
+}
+
+// dsdtm_track_frames: the same for n independent frames. Every workgroup belongs to ONE frame (its columns are padded to whole
+// workgroups): it reads that frame's Run pose and count, local map and mask; the candidates carry their frame (cand_frame), so
+// the FindMatchDirect half reads the frame's pose and its pyramid in the slab (cur_pyr + frame * pyr_pitch). The XCD-aware
+// numbering keeps consecutive workgroups — one frame's candidates — on one L2. The first workgroup of a frame seeds the
+// frame's refinement pose.
+static_assert(TRACK_COL_GROUP == MATCH_G, "columns of the batch are padded to the match kernel's group");
+__global__ __launch_bounds__(256) void track_match_batch_kernel(const TrackArgs t, const WarpKernelArgs a, const A2DKernelArgs b) {
+    __shared__ MatchShared<MATCH_G> sh;
+    __shared__ double s_T[12];
+    __shared__ int s_lost;
+    unsigned lb = blockIdx.x;
+    {
+        const unsigned q = gridDim.x / 8u;
+        if (!a.no_xcd && lb < q * 8u) lb = (lb % 8u) * q + lb / 8u;
+    }
+    const int f = t.blk_frame[lb];
+    const int c0 = t.f_col0[f];
+    const int cb = (int)lb * MATCH_G;
+    const int tid = threadIdx.x;
+    const int left = c0 + t.f_np[f] - cb;
+    const int nb = left < MATCH_G ? (left > 0 ? left : 0) : MATCH_G;
+    if (tid < 12) s_T[tid] = t.T_run[12 * (size_t)f + tid];
+    if (tid == 12) s_lost = (t.n_tracked[f] < t.min_tracked) ? 1 : 0;
+    __syncthreads();
+    if (cb == c0 && tid < 12) t.T_opt[12 * (size_t)f + tid] = s_T[tid];
+    if (tid < nb) {
+        reproject_point<true>(t, cb + tid, s_T, s_lost != 0, f, t.f_mask[f]);
+        sh.c[tid] = warp_candidate(a, cb + tid);
+        sh.sl[tid] = a.search_level[cb + tid];
     }
     __syncthreads();
     match_rounds<MATCH_G>(a, b, sh, cb, nb, tid);
@@ -217,13 +256,18 @@ void track_disc_half_widths(int radius, int8_t* hw) {
 
 size_t track_replay_lds_bytes(int n_points, int n_cells, int radius) { return replay_layout(nullptr, n_points, n_cells, radius).bytes; }
 
-template <int EPT, int NT = RP_THREADS>
-__global__ __launch_bounds__(NT) void track_replay_kernel(const TrackArgs a) {
+// The replay of one frame. BATCH (dsdtm_track_frames): workgroup f replays frame f — its columns from f_col0[f], its match list,
+// counts and refinement columns at its own offsets; the other instantiation is dsdtm_track_frame's (offsets 0).
+template <int EPT, int NT, bool BATCH>
+__device__ __forceinline__ void track_replay_body(const TrackArgs& a) {
     static_assert(NT % 64 == 0 && NT <= RP_THREADS, "threads of the replay workgroup");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     __shared__ int s_overflow, s_n_in;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int M = a.n_points, cells = a.grid_cols * a.grid_rows, R = a.cell_size, cols = a.grid_cols;
+    const int fr = BATCH ? (int)blockIdx.x : 0;
+    const size_t c0 = BATCH ? (size_t)a.f_col0[fr] : 0;             // first column of the frame
+    const size_t k0 = BATCH ? (size_t)fr * (size_t)a.max_matches : 0;   // first match / refinement feature of the frame
+    const int M = BATCH ? a.f_np[fr] : a.n_points, cells = a.grid_cols * a.grid_rows, R = a.cell_size, cols = a.grid_cols;
     const ReplayLds L = replay_layout(lds_raw, M, cells, R);
     for (int c = tid; c <= cells; c += NT) L.hist[c] = 0u;
     if (tid == 0) s_overflow = 0;
@@ -243,14 +287,14 @@ __global__ __launch_bounds__(NT) void track_replay_kernel(const TrackArgs a) {
         key[e] = ~0ull;
         cp[e] = cq[e] = 0u; csl[e] = 0;
         if (i < M) {
-            const int c = a.cell[i];
-            const int f = a.mp_found[i];
+            const int c = a.cell[c0 + i];
+            const int f = a.mp_found[c0 + i];
             // ReprojectCell: IsBad (:93), mask (:96), FindMatchDirect false (:101-104) — none of them has a side effect, so a
             // candidate that fails any of them is simply not there
-            const bool ok = a.converged[i] != 0 && a.mp_bad[i] == 0 && a.init_blocked[i] == 0;
-            const double u0 = a.px0[2 * (size_t)i], v0 = a.px0[2 * (size_t)i + 1];
-            const double u1 = a.px[2 * (size_t)i], v1 = a.px[2 * (size_t)i + 1];
-            const int sl = a.search_level[i];
+            const bool ok = a.converged[c0 + i] != 0 && a.mp_bad[c0 + i] == 0 && a.init_blocked[c0 + i] == 0;
+            const double u0 = a.px0[2 * (c0 + i)], v0 = a.px0[2 * (c0 + i) + 1];
+            const double u1 = a.px[2 * (c0 + i)], v1 = a.px[2 * (c0 + i) + 1];
+            const int sl = a.search_level[c0 + i];
             if (c >= 0 && c < cells) {
                 kcell[e] = c;
                 key[e] = ((unsigned long long)(uint32_t)(0x7fffffffll - (long long)f) << 16) | (unsigned long long)i;   // :88,:123-126 (stable: list order)
@@ -483,31 +527,48 @@ __global__ __launch_bounds__(NT) void track_replay_kernel(const TrackArgs a) {
         if (!(r < n_in && L.state[r] == ST_ACCEPTED)) continue;
         if (k < (uint32_t)a.max_matches) {
             const int i = my_idx[e];
-            const float fx_ = (float)a.px[2 * (size_t)i], fy_ = (float)a.px[2 * (size_t)i + 1];     // Feature(px as cv::Point2f, :108)
+            const float fx_ = (float)a.px[2 * (c0 + i)], fy_ = (float)a.px[2 * (c0 + i) + 1];     // Feature(px as cv::Point2f, :108)
             const int lvl = (int)L.sl[r];
             dsdtm_track_match mo;
             mo.cell = (int)L.rcell[r]; mo.point = i; mo.px[0] = fx_; mo.px[1] = fy_; mo.level = lvl;
-            a.matches[k] = mo;
+            a.matches[k0 + k] = mo;
             // Frame::Add_Feature (src/Frame.cpp:83-92): mNormal = Pixel2Camera(cv::Point2f, 1.0f) in float, normalised in double
             const float one = 1.0f;
             const double bx = (double)((one * (fx_ - a.cx)) / a.fx), by = (double)((one * (fy_ - a.cy)) / a.fy);
             const double n = sqrt(bx * bx + by * by + 1.0 * 1.0);
-            a.po_bearing[3 * (size_t)k] = bx / n; a.po_bearing[3 * (size_t)k + 1] = by / n; a.po_bearing[3 * (size_t)k + 2] = 1.0 / n;
-            a.po_world[3 * (size_t)k] = a.pw[3 * (size_t)i]; a.po_world[3 * (size_t)k + 1] = a.pw[3 * (size_t)i + 1];
-            a.po_world[3 * (size_t)k + 2] = a.pw[3 * (size_t)i + 2];
-            a.po_level[k] = lvl; a.po_use[k] = 1;
+            a.po_bearing[3 * (k0 + k)] = bx / n; a.po_bearing[3 * (k0 + k) + 1] = by / n; a.po_bearing[3 * (k0 + k) + 2] = 1.0 / n;
+            a.po_world[3 * (k0 + k)] = a.pw[3 * (c0 + i)]; a.po_world[3 * (k0 + k) + 1] = a.pw[3 * (c0 + i) + 1];
+            a.po_world[3 * (k0 + k) + 2] = a.pw[3 * (c0 + i) + 2];
+            a.po_level[k0 + k] = lvl; a.po_use[k0 + k] = 1;
         }
         k++;
     }
     if (tid == 0) {
         const int nm = (int)(total < (uint32_t)a.max_matches ? total : (uint32_t)a.max_matches);
-        a.po_n[0] = nm;
-        a.counts[0] = n_in; a.counts[1] = nm; a.counts[2] = unsettled ? 2 : (scan_all ? 1 : 0);   // 0 masks, 1 full scan, 2 did not settle (a bug)
+        a.po_n[fr] = nm;
+        a.counts[4 * fr] = n_in; a.counts[4 * fr + 1] = nm; a.counts[4 * fr + 2] = unsettled ? 2 : (scan_all ? 1 : 0);   // 0 masks, 1 full scan, 2 did not settle (a bug)
     }
+}
+
+template <int EPT, int NT = RP_THREADS>
+__global__ __launch_bounds__(NT) void track_replay_kernel(const TrackArgs a) {
+    track_replay_body<EPT, NT, false>(a);
+}
+
+// dsdtm_track_frames: one 1024-thread workgroup per frame (blockIdx.x = frame); dynamic LDS sized by the largest frame
+template <int EPT>
+__global__ __launch_bounds__(RP_THREADS) void track_replay_batch_kernel(const TrackArgs a) {
+    track_replay_body<EPT, RP_THREADS, true>(a);
 }
 
 hipError_t track_match_launch(const TrackArgs& t, const WarpKernelArgs& wa, const A2DKernelArgs& aa, hipStream_t stream) {
     if (wa.m != t.n_points || aa.m != t.n_points || t.run_out_n16 < 0 || t.run_out_n16 > 192) return hipErrorInvalidValue;
+    if (t.n_frames > 0) {                                          // dsdtm_track_frames: the columns are whole workgroups
+        if (t.n_points <= 0 || t.n_points % MATCH_G || !t.blk_frame || !t.f_col0 || !t.f_np || !t.f_mask || !t.in_grid)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(track_match_batch_kernel, dim3((unsigned)(t.n_points / MATCH_G)), dim3(256), 0, stream, t, wa, aa);
+        return hipGetLastError();
+    }
     // (at least one workgroup: block 0 also forwards Run's results and seeds the refinement's pose)
     const int blocks = t.n_points > 0 ? (t.n_points + MATCH_G - 1) / MATCH_G : 1;
     hipLaunchKernelGGL(track_match_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, t, wa, aa);
@@ -520,7 +581,26 @@ static hipError_t replay_optin(size_t bytes) {
     return hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+template <int EPT>
+static hipError_t replay_batch(const TrackArgs& a, size_t lds, hipStream_t stream) {
+    if (lds > 48 * 1024) {
+        const hipError_t e = replay_optin<track_replay_batch_kernel<EPT>>(lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(track_replay_batch_kernel<EPT>, dim3((unsigned)a.n_frames), dim3(RP_THREADS), lds, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t track_replay_launch(const TrackArgs& a, hipStream_t stream) {
+    if (a.n_frames > 0) {                                          // dsdtm_track_frames: workgroup f = frame f
+        if (!a.f_col0 || !a.f_np || a.max_points < 0 || a.max_points > 4096) return hipErrorInvalidValue;
+        const size_t lds = track_replay_lds_bytes(a.max_points, a.grid_cols * a.grid_rows, a.cell_size);
+        if (lds > 160 * 1024 - 256) return hipErrorInvalidValue;
+        const int ept = (a.max_points + RP_THREADS - 1) / RP_THREADS;
+        if (ept <= 1) return replay_batch<1>(a, lds, stream);
+        if (ept <= 2) return replay_batch<2>(a, lds, stream);
+        return replay_batch<4>(a, lds, stream);
+    }
     const size_t lds = track_replay_lds_bytes(a.n_points, a.grid_cols * a.grid_rows, a.cell_size);
     if (lds > 160 * 1024 - 256) return hipErrorInvalidValue;
     const int ept = (a.n_points + RP_THREADS - 1) / RP_THREADS;

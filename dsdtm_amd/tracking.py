@@ -115,6 +115,80 @@ def track_frame(ctx: capi.Context, cam, image, levels, last: Frame, T_seed, alig
     return TrackCall(ctx, cam, image, levels, last, T_seed, align, min_tracked, keyframes, map_points, **kw).run()
 
 
+class TrackBatchCall:
+    """One prepared dsdtm_track_frames call: n frames of n independent trackers (each described as for TrackCall: a dict of
+    TrackCall's arguments), descriptors built once, `run()` the library call alone. Every frame's result equals its TrackCall's;
+    each one also carries `in_grid` (uint8 per map point: 1 = ReprojectPoint put it into the grid, i.e. into mvpLocalMapPoints)."""
+
+    def __init__(self, ctx: capi.Context, cam, frames):
+        self.ctx = ctx
+        self.calls = [TrackCall(ctx, cam, **f) for f in frames]
+        n = len(self.calls)
+        self.n = n
+        self.descs = (capi.TrackDesc * max(1, n))(*[c.desc for c in self.calls])
+        self.res = (capi.TrackResult * max(1, n))()
+        self.max_matches = int(self.calls[0].desc.max_matches) if n else 1
+        self.matches = np.zeros(max(1, n * self.max_matches), capi.TRACK_MATCH_DTYPE)
+        self.rn = np.zeros(max(1, n * self.max_matches))
+        self.n_points = [int(c.desc.n_points) for c in self.calls]
+        self.grid_at = np.concatenate([[0], np.cumsum(self.n_points)]).astype(np.int64)
+        self.in_grid = np.zeros(max(1, int(self.grid_at[-1])), np.uint8)
+        self.cs = capi.camera_struct(cam)
+
+    def run_raw(self) -> int:
+        """The library call alone; returns its status (the new frames' handles are in self.res[f].frame)."""
+        return self.ctx.lib.dsdtm_track_frames(self.ctx.handle, C.byref(self.cs), self.n, self.descs, self.res, self.matches.ctypes.data,
+                                               self.rn.ctypes.data, self.in_grid.ctypes.data)
+
+    def run(self) -> list:
+        self.ctx.check(self.run_raw())
+        out = []
+        for f in range(self.n):
+            res = self.res[f]
+            sm = res.summary.as_dict()
+            m0 = f * self.max_matches
+            out.append(dict(frame=capi.DeviceFrame(self.ctx, C.c_void_p(res.frame)), T_run=np.array(list(res.T_run)).reshape(3, 4),
+                            n_tracked=int(res.n_tracked), lost=bool(res.lost), stats=res.stats.as_dict(), n_in_grid=int(res.n_in_grid),
+                            replay_full_scan=bool(res.replay_full_scan), matches=self.matches[m0:m0 + res.n_matches].copy(),
+                            T_opt=np.array(list(res.T_opt)).reshape(3, 4), summary=sm,
+                            residual_norm=self.rn[m0:m0 + sm["n_residual_blocks"]].copy(),
+                            in_grid=self.in_grid[self.grid_at[f]:self.grid_at[f + 1]].copy()))
+        return out
+
+
+def track_frames(ctx: capi.Context, cam, frames) -> list:
+    """dsdtm_track_frames: `frames` is a list of dicts of track_frame's arguments after `cam` (image, levels, last, T_seed, align,
+    min_tracked, keyframes, map_points, and its keywords). Returns one track_frame result per frame, plus `in_grid`."""
+    if not frames:
+        return []
+    return TrackBatchCall(ctx, cam, frames).run()
+
+
+def apply_tracked_frame(cam, image, r, map_points, img_mask=None):
+    """The reference's side effects of one tracked frame (src/Tracking.cpp:199-256) from a track_frame / track_frames result:
+    returns (cur Frame, n_tracked, matches as [(cell, MapPoint, px float32[2], level)])."""
+    cur = Frame(cam, [np.ascontiguousarray(image, np.uint8)], r["T_run"])              # (level 0 only on the host: the pyramid is on the device)
+    cur._device_frame = r["frame"]
+    if r["lost"]:                                                                      # :208-214
+        return cur, r["n_tracked"], []
+    m = r["matches"]
+    mps = [map_points[int(i)] for i in m["point"]]
+    for mp in mps:
+        mp.IncreaseFound()                                                             # src/Feature_alignment.cpp:106
+    if img_mask is not None:
+        for q in m["px"]:                                                              # :111 (cv::Point from Point2d rounds)
+            search.fill_circle(img_mask, search.cvRound(float(q[0])), search.cvRound(float(q[1])), int(Config.Get("Camera.CellSize")), 0)
+    if len(m):
+        search.add_matched_features(cur, m["px"], m["level"], mps)                     # :108-114
+    cur.Set_Pose(r["T_opt"])                                                           # src/Optimizer.cpp:78
+    thresh = float(np.float32(Config.Get("Optimization.LocalBAthreshhold"))) / float(np.float32(cam.f))
+    rn = r["residual_norm"]
+    for i in range(len(rn)):                                                           # :80-92 (every feature has a block here: index = block)
+        if rn[i] > thresh and not mps[i].IsBad():
+            mps[i].EraseFound()
+    return cur, r["n_tracked"], [(int(m["cell"][k]), mps[k], m["px"][k].copy(), int(m["level"][k])) for k in range(len(m))]
+
+
 class Tracker:
     """Tracking's per-frame flow (src/Tracking.cpp:199-256) on top of track_frame, with the reference's side effects: the new
     Frame gets the pose, the features SearchLocalPoints creates (px, level, bearing, map point, mbInitial) and the refined
@@ -136,23 +210,33 @@ class Tracker:
                         (self.levels, self.min_level, self.max_iters, int(Config.Get("Camera.Min_fts"))), self.min_tracked,
                         keyframes, map_points, mask=img_mask)
         self.last_result = r
-        cur = Frame(self.cam, [np.ascontiguousarray(image, np.uint8)], r["T_run"])      # (level 0 only on the host: the pyramid is on the device)
-        cur._device_frame = r["frame"]
-        if r["lost"]:                                                                  # :208-214
-            return cur, r["n_tracked"], []
-        m = r["matches"]
-        mps = [map_points[int(i)] for i in m["point"]]
-        for mp in mps:
-            mp.IncreaseFound()                                                         # src/Feature_alignment.cpp:106
-        if img_mask is not None:
-            for q in m["px"]:                                                          # :111 (cv::Point from Point2d rounds)
-                search.fill_circle(img_mask, search.cvRound(float(q[0])), search.cvRound(float(q[1])), int(Config.Get("Camera.CellSize")), 0)
-        if len(m):
-            search.add_matched_features(cur, m["px"], m["level"], mps)                 # :108-114
-        cur.Set_Pose(r["T_opt"])                                                       # src/Optimizer.cpp:78
-        thresh = float(np.float32(Config.Get("Optimization.LocalBAthreshhold"))) / float(np.float32(self.cam.f))
-        rn = r["residual_norm"]
-        for i in range(len(rn)):                                                       # :80-92 (every feature has a block here: index = block)
-            if rn[i] > thresh and not mps[i].IsBad():
-                mps[i].EraseFound()
-        return cur, r["n_tracked"], [(int(m["cell"][k]), mps[k], m["px"][k].copy(), int(m["level"][k])) for k in range(len(m))]
+        return apply_tracked_frame(self.cam, image, r, map_points, img_mask)
+
+
+class MultiTracker:
+    """Tracker.TrackFrame for n independent sequences at once (a multi-camera rig, offline re-tracking, many robots): one
+    dsdtm_track_frames call per step, then the reference's side effects per sequence, as Tracker.TrackFrame applies them.
+    All sequences share the camera and the tracking parameters. Each result also keeps the local map points ReprojectPoint
+    put into the grid (`last_results[i]["local_map_points"]`: UpdateLocalMap's mvpLocalMapPoints, src/Tracking.cpp:299-304, empty
+    for a lost frame) — the candidates of the caller's IsinFrustum -> IncreaseVisible() step."""
+
+    def __init__(self, camera, ctx: capi.Context | None = None, max_level=None, min_level=None, max_iters=None, min_tracked=20):
+        self.t = Tracker(camera, ctx, max_level, min_level, max_iters, min_tracked)
+        self.cam, self.ctx = camera, self.t.ctx
+        self.last_results = []
+
+    def TrackFrames(self, images, lasts, keyframes, map_points, img_masks=None):
+        """Lists of n (one per sequence). Returns [(cur Frame, n_tracked, matches)] as Tracker.TrackFrame does per sequence."""
+        n = len(images)
+        img_masks = img_masks if img_masks is not None else [None] * n
+        align = (self.t.levels, self.t.min_level, self.t.max_iters, int(Config.Get("Camera.Min_fts")))
+        frames = [dict(image=images[i], levels=self.t.levels, last=lasts[i], T_seed=lasts[i].Get_Pose(), align=align,
+                       min_tracked=self.t.min_tracked, keyframes=keyframes[i], map_points=map_points[i], mask=img_masks[i])
+                  for i in range(n)]
+        rs = track_frames(self.ctx, self.cam, frames)
+        out = []
+        for i, r in enumerate(rs):
+            r["local_map_points"] = [map_points[i][j] for j in np.flatnonzero(r["in_grid"])]
+            out.append(apply_tracked_frame(self.cam, images[i], r, map_points[i], img_masks[i]))
+        self.last_results = rs
+        return out

@@ -425,6 +425,29 @@ typedef struct dsdtm_track_result {
 int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* desc,
                       dsdtm_track_result* result, dsdtm_track_match* matches, double* residual_norm);
 
+/* ---- n independent tracked frames in ONE submission ------------------------------------------------------------------
+ * dsdtm_track_frame for the frames of n independent trackers (a multi-camera rig, offline re-tracking of a dataset, many
+ * robots on one server): one call, one submission, one wait. Per frame the results are those of dsdtm_track_frame on the same
+ * descriptor, bit for bit — T_run, n_tracked, stats, lost, n_in_grid, the matches, replay_full_scan, T_opt, summary, the
+ * residual norms and the returned frame's pyramid — except that Run never runs a pair over several compute units here (a frame
+ * of 449..704 reference features takes the one-CU kernel, as dsdtm_track_frame does when teams are switched off).
+ * Shared by all frames (DSDTM_ERR_INVALID naming the frame and the field otherwise): the camera, width, height, levels, align,
+ * min_tracked, cell_size, max_pyr_levels, max_matches, align2d_iters, pose_opt. Everything else is per frame: image (any of the
+ * memories dsdtm_track_frame accepts), reference frame and features, T_ref_w, T_seed, keyframes, local map, observations, mask.
+ * Limits per frame: those of dsdtm_track_frame, and n_ref_features <= 704; 1 <= n_frames <= DSDTM_TRACK_FRAMES_MAX
+ * (n_frames == 0: DSDTM_OK, nothing done).
+ * All or nothing: every frame is checked before anything is enqueued; on any error no frame is handed out (results[f].frame ==
+ * NULL for every f) and nothing leaks.
+ * results: n_frames; matches and residual_norm: n_frames * max_matches, frame f's from f * max_matches; in_grid (or NULL): the
+ * sum of descs[f].n_points bytes, the frames back to back in order — 1 where ReprojectPoint put the point into the grid
+ * (src/Feature_alignment.cpp:54-69: not bad, inside the image), i.e. the points UpdateLocalMap adds to mvpLocalMapPoints
+ * (src/Tracking.cpp:299-304); all 0 for a lost frame, whose UpdateLocalMap the reference skips. Their sum is n_in_grid.
+ * The returned frames are ordinary dsdtm_frames (one allocation is shared by the frames of a call and released with the last
+ * of them): destroyed on their own, in any order, and usable as ref / kf by any entry that takes a frame. */
+#define DSDTM_TRACK_FRAMES_MAX 1024
+int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n_frames, const dsdtm_track_desc* descs,
+                       dsdtm_track_result* results, dsdtm_track_match* matches, double* residual_norm, uint8_t* in_grid);
+
 /* Enqueues the alignment of all pairs on `hip_stream` (a hipStream_t, NULL = default
  * stream). Asynchronous: results are valid after the stream is synchronised. */
 int dsdtm_sparse_align_batch_device(dsdtm_ctx* ctx, const dsdtm_batch_desc* batch,
