@@ -141,7 +141,7 @@ EXPORTED_SYMBOLS = [
     "dsdtm_pose_optimization", "dsdtm_pose_optimization_batch_device",
     "dsdtm_sparse_align_batch_sharded", "dsdtm_sparse_align_batch_streamed", "dsdtm_shard_range", "dsdtm_detect_cells_batch_device",
     "dsdtm_match_candidates_batch_device", "dsdtm_match_candidates_scratch_bytes", "dsdtm_track_frame",
-    "dsdtm_track_frames",
+    "dsdtm_track_frames", "dsdtm_local_ba", "dsdtm_local_ba_batch_device",
 ]
 
 
@@ -163,6 +163,33 @@ class PoseOptSummary(C.Structure):
         return dict(iterations=self.iterations, successful_steps=self.successful_steps, termination=self.termination,
                     n_residual_blocks=self.n_residual_blocks, initial_cost=self.initial_cost,
                     final_cost=self.final_cost, x=np.array(list(self.x)))
+
+
+class LocalBaParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("reserved", C.c_int32), ("delta", C.c_double)]
+
+
+class LocalBaSummary(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("successful_steps", C.c_int32), ("termination", C.c_int32),
+                ("n_residual_blocks", C.c_int32), ("n_outliers", C.c_int32), ("n_free_keyframes", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+LBA_SUMMARY_DTYPE = np.dtype([("iterations", "<i4"), ("successful_steps", "<i4"), ("termination", "<i4"),
+                              ("n_residual_blocks", "<i4"), ("n_outliers", "<i4"), ("n_free_keyframes", "<i4"),
+                              ("initial_cost", "<f8"), ("final_cost", "<f8")])
+assert LBA_SUMMARY_DTYPE.itemsize == C.sizeof(LocalBaSummary)
+
+
+class LocalBaProblem(C.Structure):
+    _fields_ = [("n_keyframes", C.c_int32), ("n_points", C.c_int32), ("n_observations", C.c_int32), ("reserved", C.c_int32),
+                ("keyframe_offset", C.c_int64), ("point_offset", C.c_int64), ("observation_offset", C.c_int64)]
+
+
+LBA_MAX_FREE_KF, LBA_MAX_CONST_KF, LBA_MAX_POINTS, LBA_MAX_OBSERVATIONS = 16, 64, 16384, 131072
 
 
 class TrackDesc(C.Structure):

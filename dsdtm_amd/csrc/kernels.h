@@ -236,6 +236,30 @@ hipError_t track_replay_launch(const TrackArgs& args, hipStream_t stream);
 size_t track_replay_lds_bytes(int n_points, int n_cells, int radius);
 void track_disc_half_widths(int radius, int8_t* hw);   // radius <= 127
 
+// Local bundle adjustment (Optimizer::LocalBundleAdjustment): one workgroup per problem (local_ba.hip).
+struct LocalBaProblemDev {
+    int32_t n_kf, n_pts, n_obs, reserved;
+    int64_t kf_off, pt_off, obs_off;   // elements
+    int64_t ws_off;                    // bytes into ws (local_ba_workspace_bytes of the problem, 256-aligned)
+};
+struct LocalBaArgs {
+    int n_problems, max_iterations;
+    double delta;
+    const LocalBaProblemDev* problems;
+    double* T; const uint8_t* kf_const; double* points;
+    const int32_t* obs_kf; const int32_t* obs_pt; const double* bearing; const int32_t* level;
+    uint8_t* outlier; dsdtm_local_ba_summary* summary;
+    uint8_t* ws;
+    int32_t* check;                    // n_problems: local_ba_check_kernel's masks (LBA_CHECK_*)
+};
+enum {
+    LBA_CHECK_KF_INDEX = 1, LBA_CHECK_POINT_INDEX = 2, LBA_CHECK_LEVEL = 4, LBA_CHECK_ORDER = 8, LBA_CHECK_DUPLICATE = 16,
+    LBA_CHECK_NO_FREE = 32, LBA_CHECK_FREE_LIMIT = 64, LBA_CHECK_CONST_LIMIT = 128
+};
+size_t local_ba_workspace_bytes(int n_pts, int n_obs);
+hipError_t local_ba_check_launch(const LocalBaArgs& args, hipStream_t stream);   // the device-side checks (reads only)
+hipError_t local_ba_launch(const LocalBaArgs& args, hipStream_t stream);         // the solve, on checked problems
+
 #ifdef DSDTM_DIAG
 // device self-test of the FP64 building blocks (wave reduction, LDLT, SE3); see selftest.hip (diagnostic build only)
 hipError_t selftest_launch(const double* in, double* out, int n_cases, hipStream_t stream);

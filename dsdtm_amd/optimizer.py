@@ -4,6 +4,10 @@ src/Tracking.cpp:236) over the C ABI. The solve — every residual/Jacobian eval
 trust-region iterations, the final residual norms — is one library call (dsdtm_pose_optimization,
 HIP, one wavefront); what is left here is the reference's bookkeeping on MapPoint objects (:80-92).
 
+Optimizer::LocalBundleAdjustment (src/Optimizer.cpp:103-282, called by LocalMapping::Run for every new keyframe) the
+same way: the solve and the outlier test are one call (dsdtm_local_ba, HIP, one workgroup), the set construction,
+write-back and outlier bookkeeping stay here, on KeyFrame / MapPoint objects (dsdtm_amd.mapping has minimal ones).
+
 There is no CPU path for the solve.
 """
 from __future__ import annotations
@@ -58,6 +62,76 @@ class Optimizer:
         Optimizer.last_summary = sm
         return sm
 
+    @staticmethod
+    def LocalBundleAdjustment(tKFrame, tMap=None, ctx: capi.Context | None = None, solve=None):
+        """src/Optimizer.cpp:103-282 on duck-typed keyframes (mlId, mlLocalBAKfId, mlFixedLocalBAKfId, mvMapPoints,
+        mvFeatures[i].mNormal / .mlevel, mCamera.mf, Get_Pose / Set_Pose, GetCovKFrames, Erase_MapPointMatch) and map
+        points (mlID, mlLocalBAKFId, IsBad, Get_Pose / Set_Pose, Get_Observations, Erase_Observation). tMap is only
+        the reference's lock holder. `solve` replaces the library call (tests of the bookkeeping); it takes and returns
+        what local_bundle_adjustment does. Returns the solver summary (+ "n_outliers")."""
+        cam = tKFrame.mCamera                                    # :105-106: double(float threshold) / float mf
+        mf = cam.mf if hasattr(cam, "mf") else cam.f
+        thresh = float(np.float32(Config.Get("Optimization.LocalBAthreshhold"))) / float(np.float32(mf))
+        local_kfs = [tKFrame]                                    # :110-121
+        for _, kf in tKFrame.GetCovKFrames():
+            kf.mlLocalBAKfId = tKFrame.mlId
+            local_kfs.append(kf)
+        local_mps = []                                           # :123-141
+        for kf in local_kfs:
+            for mp in list(kf.mvMapPoints):
+                if mp is None or mp.IsBad():
+                    continue
+                if mp.mlLocalBAKFId != tKFrame.mlId:
+                    mp.mlLocalBAKFId = tKFrame.mlId
+                    local_mps.append(mp)
+        fixed_kfs = []                                           # :143-159
+        for mp in local_mps:
+            for kf in mp.Get_Observations():
+                if kf.mlLocalBAKfId != tKFrame.mlId and kf.mlFixedLocalBAKfId != tKFrame.mlId:
+                    kf.mlFixedLocalBAKfId = tKFrame.mlId
+                    fixed_kfs.append(kf)
+        # parameter blocks (:166-200): keyed by mlId as tKFPoseSets is, local keyframes first
+        kf_index, kfs, const = {}, [], []
+        for kf, fixed in [(k, False) for k in local_kfs] + [(k, True) for k in fixed_kfs]:
+            if kf.mlId in kf_index:
+                if fixed:
+                    const[kf_index[kf.mlId]] = True              # SetParameterBlockConstant on the same block
+                continue
+            kf_index[kf.mlId] = len(kfs)
+            kfs.append(kf)
+            const.append(fixed or kf.mlId == 0)
+        # residual blocks (:202-224): points in tvLocalMapPoints order, then their observations in map order
+        obs_kf, obs_pt, bearing, level, pairs = [], [], [], [], []
+        for q, mp in enumerate(local_mps):
+            for kf, idx in mp.Get_Observations().items():
+                if kf.mlId not in kf_index:
+                    continue
+                ft = kf.mvFeatures[idx]
+                obs_kf.append(kf_index[kf.mlId]); obs_pt.append(q)
+                bearing.append(np.asarray(ft.mNormal, np.float64)); level.append(int(ft.mlevel))
+                pairs.append((mp, kf))
+        T = np.stack([np.asarray(kf.Get_Pose(), np.float64).reshape(3, 4) for kf in kfs]).reshape(-1).copy()
+        X = np.stack([np.asarray(mp.Get_Pose(), np.float64).reshape(3) for mp in local_mps]).reshape(-1).copy() \
+            if local_mps else np.zeros(0)
+        args = (T, np.asarray(const, np.uint8), X, np.asarray(obs_kf, np.int32), np.asarray(obs_pt, np.int32),
+                np.asarray(bearing, np.float64).reshape(-1, 3), np.asarray(level, np.int32), thresh)
+        if solve is None:
+            out, sm = local_bundle_adjustment(ctx or capi.default_context(), *args)
+        else:
+            out, sm = solve(*args)
+        for k, kf in enumerate(kfs):                             # :236-242 (every keyframe, fixed ones included)
+            kf.Set_Pose(T.reshape(-1, 3, 4)[k].copy())
+        for q, mp in enumerate(local_mps):                       # :244-248
+            mp.Set_Pose(X.reshape(-1, 3)[q].copy())
+        # :250-271 — Erase_Observation runs first, so Erase_MapPointMatch finds no index (Get_IndexInKeyFrame == -1) and
+        # the keyframe's mvMapPoints entry stays; Erase_Observation sets a point left with <= 1 observation bad
+        for i in np.nonzero(out)[0]:
+            mp, kf = pairs[i]
+            mp.Erase_Observation(kf)
+            kf.Erase_MapPointMatch(mp)
+        Optimizer.last_summary = sm
+        return sm
+
 
 def pose_optimization(ctx: capi.Context, bearing, p_world, level, use, T_cur_w, max_iterations: int = 100):
     """dsdtm_pose_optimization: T_cur_w (12 doubles) is updated in place; returns (residual norms in
@@ -82,3 +156,31 @@ def pose_optimization(ctx: capi.Context, bearing, p_world, level, use, T_cur_w, 
                 C.byref(sm)))
     d = sm.as_dict()
     return rn[:d["n_residual_blocks"]].copy(), d
+
+
+def local_bundle_adjustment(ctx: capi.Context, T_c2w, kf_constant, points, obs_kf, obs_point, obs_bearing, obs_level,
+                            delta: float, max_iterations: int = 10):
+    """dsdtm_local_ba: T_c2w (12 doubles per keyframe) and points (3 per point) are float64 C-contiguous arrays updated in
+    place; returns (outlier flags per observation, summary dict)."""
+    for a in (T_c2w, points):
+        assert a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable
+    K, NP = T_c2w.size // 12, points.size // 3
+    kc = np.ascontiguousarray(kf_constant, np.uint8)
+    okf = np.ascontiguousarray(obs_kf, np.int32)
+    opt = np.ascontiguousarray(obs_point, np.int32)
+    b = np.ascontiguousarray(obs_bearing, np.float64).reshape(-1, 3)
+    lev = np.ascontiguousarray(obs_level, np.int32)
+    N = len(okf)
+    assert len(kc) == K and len(opt) == N and len(b) == N and len(lev) == N
+    out = np.zeros(max(N, 1), np.uint8)
+    prm = capi.LocalBaParams(int(max_iterations), 0, float(delta))
+    sm = capi.LocalBaSummary()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    f = ctx.lib.dsdtm_local_ba
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_int, dp, capi.u8p, C.c_int, dp, C.c_int, ip, ip, dp, ip, C.POINTER(capi.LocalBaParams),
+                  capi.u8p, C.POINTER(capi.LocalBaSummary)]
+    ctx.check(f(ctx.handle, K, T_c2w.ctypes.data_as(dp), kc.ctypes.data_as(capi.u8p), NP, points.ctypes.data_as(dp), N,
+                okf.ctypes.data_as(ip), opt.ctypes.data_as(ip), b.ctypes.data_as(dp), lev.ctypes.data_as(ip), C.byref(prm),
+                out.ctypes.data_as(capi.u8p), C.byref(sm)))
+    return out[:N].copy(), sm.as_dict()

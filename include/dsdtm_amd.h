@@ -622,6 +622,77 @@ int dsdtm_warp_patches(dsdtm_ctx* ctx, const dsdtm_pyramid* kf_pyr, int n_kf,
                        double* affine, int32_t* search_level,
                        uint8_t* patch_border, uint8_t* patch);
 
+/* ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cpp:103-282) ----------------------------------------------------
+ * The solve and the outlier pass of local BA, on the device; the set construction (local keyframes = tKFrame, then
+ * GetCovKFrames() :110-121; local points = their non-bad points, each once :123-141; fixed keyframes = every other
+ * observer of a local point :143-159) stays with the caller (dsdtm_amd/optimizer.py).
+ *   - one 6-parameter block [t, log R] per keyframe; constant when kf_constant[k] != 0 (the fixed keyframes :168-181 and a
+ *     local keyframe with mlId == 0 :182-183). A free keyframe without observations is left alone (Ceres removes it)
+ *   - one free 3-parameter block per point (:195-200); a point without observations is left alone
+ *   - one FullBA_Problem residual per observation (include/Optimizer.h:129-216: residual / (1 << level), Jacobians NOT
+ *     divided; point Jacobian -[1/z, 0, -x/z^2; 0, 1/z, -y/z^2] R), HuberLoss(delta) (:163)
+ *   - Ceres 1.13 trust-region Levenberg-Marquardt, DENSE_SCHUR (points eliminated), at most max_iterations (:226-233),
+ *     restated as DESIGN.md §3.7 describes; deterministic (fixed summation order): a problem gives the same bits alone
+ *     or in any batch, run after run
+ *   - write-back :236-248: every keyframe, constant ones included, gets SE3(SO3::exp(x.tail), x.head) — a constant pose
+ *     comes back re-normalised, not byte-identical; every point its new position
+ *   - outlier pass :250-271: outlier[i] = |n.xy / n.z - (T p).xy / (T p).z|^2 > delta^2 at the new poses
+ *     (utils::ReprojectionError, include/Utils.h:20-27: not divided by the level, compared with delta squared)
+ * The caller does the bookkeeping of each outlier (Erase_Observation, Erase_MapPointMatch).
+ *
+ * T_c2w       : n_keyframes x 12 doubles, [R|t] 3x4 row-major KeyFrame::Get_Pose() (world -> camera); in/out
+ * kf_constant : n_keyframes bytes
+ * points      : n_points x 3 doubles, MapPoint::Get_Pose(); in/out
+ * observations, in residual-block order (points in tvLocalMapPoints order, then std::map<KeyFrame*> order :202-224):
+ *   obs_kf, obs_point : keyframe / point index of each; obs_point must not decrease (a point's observations are
+ *                       consecutive) and a keyframe observes a point at most once
+ *   obs_bearing       : n_observations x 3 doubles, Feature::mNormal;  obs_level : Feature::mlevel (0 .. DSDTM_MAX_LEVELS-1)
+ * outlier     : n_observations bytes, out
+ * Limits per problem: DSDTM_LBA_MAX_FREE_KF free (non-constant) keyframes, at least one; DSDTM_LBA_MAX_CONST_KF constant
+ * ones; DSDTM_LBA_MAX_POINTS points; DSDTM_LBA_MAX_OBSERVATIONS observations. A problem over a limit, without a free
+ * keyframe or with an index, level or order out of range returns DSDTM_ERR_INVALID (the reason in dsdtm_last_error)
+ * before anything is enqueued, and nothing is written. */
+#define DSDTM_LBA_MAX_FREE_KF 16
+#define DSDTM_LBA_MAX_CONST_KF 64
+#define DSDTM_LBA_MAX_POINTS 16384
+#define DSDTM_LBA_MAX_OBSERVATIONS 131072
+typedef struct dsdtm_local_ba_params {
+    int32_t max_iterations;   /* 10 (:232) */
+    int32_t reserved;
+    double delta;             /* Huber threshold: double(float Optimization.LocalBAthreshhold) / float mf (:105-106) */
+} dsdtm_local_ba_params;
+typedef struct dsdtm_local_ba_summary {
+    int32_t iterations;        /* trust-region iterations run */
+    int32_t successful_steps;
+    int32_t termination;       /* dsdtm_pose_opt_termination (DSDTM_PO_NO_RESIDUALS: no observation) */
+    int32_t n_residual_blocks; /* = n_observations */
+    int32_t n_outliers;        /* observations with outlier != 0 */
+    int32_t n_free_keyframes;  /* free keyframes with observations: the pose blocks of the reduced camera matrix */
+    double initial_cost, final_cost;   /* 1/2 sum rho(|r_i|^2) */
+} dsdtm_local_ba_summary;
+typedef struct dsdtm_local_ba_problem {
+    int32_t n_keyframes, n_points, n_observations, reserved;
+    int64_t keyframe_offset;    /* elements: keyframe k of this problem is keyframe keyframe_offset + k of the arrays */
+    int64_t point_offset;
+    int64_t observation_offset; /* obs_kf / obs_point index the problem's OWN keyframes and points (0-based) */
+} dsdtm_local_ba_problem;
+int dsdtm_local_ba(dsdtm_ctx* ctx, int n_keyframes, double* T_c2w, const uint8_t* kf_constant,
+                   int n_points, double* points, int n_observations, const int32_t* obs_kf, const int32_t* obs_point,
+                   const double* obs_bearing, const int32_t* obs_level, const dsdtm_local_ba_params* params,
+                   uint8_t* outlier, dsdtm_local_ba_summary* summary);
+/* n_problems independent problems (one per map or robot) in ONE launch, one workgroup per problem. `problems` is a HOST
+ * array; every other pointer is a DEVICE pointer into arrays that hold the problems back to back at the offsets of their
+ * descriptors (summary: one per problem). All or nothing: the counts and offsets of every problem are checked on the host,
+ * then the indices, levels, order and constant flags (device memory) by a read-only check kernel whose verdict the call
+ * waits for; one bad problem and the call returns DSDTM_ERR_INVALID with nothing written and no solve enqueued. The solve
+ * itself is asynchronous on `hip_stream`: results are valid after the stream is synchronised. Local-BA launches of one
+ * context run one after another (the context's workspace). */
+int dsdtm_local_ba_batch_device(dsdtm_ctx* ctx, int n_problems, const dsdtm_local_ba_problem* problems,
+                                double* T_c2w, const uint8_t* kf_constant, double* points,
+                                const int32_t* obs_kf, const int32_t* obs_point, const double* obs_bearing,
+                                const int32_t* obs_level, const dsdtm_local_ba_params* params,
+                                uint8_t* outlier, dsdtm_local_ba_summary* summary, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
