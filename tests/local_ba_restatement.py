@@ -110,8 +110,20 @@ def _reduce(idx, vals, n):
     return out
 
 
-def solve(P: Problem, max_iterations=10, form="schur", mutants=(), trace=None):
-    """Returns (T (K,3,4), points (P,3), outlier (N,) u8, summary dict). L5 needs a World (its `fixed` flags)."""
+def solve(P: Problem, max_iterations=10, form="schur", mutants=(), trace=None, function_tolerance=1e-6,
+          parameter_tolerance=1e-8):
+    """Returns (T (K,3,4), points (P,3), outlier (N,) u8, summary dict). L5 needs a World (its `fixed` flags).
+    `trace` (a list) receives, in order of execution: ("step", it, radius, model_change), ("ratio", it, rho, cost,
+    model_change), and one record per tolerance test, each with the quantity and the bound it was compared with and the
+    number of steps accepted before it:
+      ("gradient", it, gmax, 1e-10, accepted, ground, sens_pose, sens_point)  ground = max_i sum_o |J_oi| rho_o with
+          rho_o = 2^-50 (|observed| + |projected|) / 2^level, what the rounding of a residual's own subtraction moves a
+          gradient component by; sens_* = max_i sum_o |J_oi| sum_j |J_oj| over the pose / point columns j: a deviation
+          of d_pose / d_point per parameter moves no gradient component by more than d_pose sens_pose + d_point sens_point
+      ("parameter", it, step_norm, 1e-8 (x_norm + 1e-8), accepted)
+      ("function", it, |cost change|, 1e-6 cost, accepted, cost)
+    function_tolerance / parameter_tolerance: Ceres' defaults, which the reference leaves alone; the tests set one to 0 to
+    polish a start, or to ask what the OTHER test would have said at the iteration the first one ended."""
     mutants = tuple(mutants)
     if "L6" in mutants:
         max_iterations = 100
@@ -146,6 +158,20 @@ def solve(P: Problem, max_iterations=10, form="schur", mutants=(), trace=None):
         gp = _reduce(col_p[P.obs_pt], np.einsum("nij,ni->nj", Jp, r), Q)
         return gk, gp
 
+    def trace_gradient(it, gmax, succ, xk_, xp_, Jc, Jp):
+        aJc, aJp = np.abs(Jc), np.abs(Jp)
+        Rm = Rotation.from_rotvec(xk_[:, 3:]).as_matrix()
+        pc = np.einsum("nij,nj->ni", Rm[P.obs_kf], xp_[P.obs_pt]) + xk_[P.obs_kf, :3]
+        rho = 2.0 ** -50 * (np.abs(P.bearing[:, :2] / P.bearing[:, 2:3]) + np.abs(pc[:, :2] / pc[:, 2:3]))
+        rho = rho / (1 << P.level).astype(np.float64)[:, None]
+        ck, cp = col_k[P.obs_kf][ok_k], col_p[P.obs_pt]
+
+        def worst(row_weight):                                   # max over the columns i of sum_o |J_oi| . weight_o
+            a = _reduce(ck, np.einsum("nij,ni->nj", aJc[ok_k], row_weight[ok_k]), F)
+            b = _reduce(cp, np.einsum("nij,ni->nj", aJp, row_weight), Q)
+            return max(a.max(initial=0.0), b.max(initial=0.0))
+        trace.append(("gradient", it, gmax, 1e-10, succ, worst(rho), worst(aJc.sum(2)), worst(aJp.sum(2))))
+
     def gmax_of(xk_, xp_, gk, gp):
         m = 0.0
         for a in range(F):
@@ -173,12 +199,15 @@ def solve(P: Problem, max_iterations=10, form="schur", mutants=(), trace=None):
             while True:
                 if it >= max_iterations:
                     term = MAX_ITER; break
+                if trace is not None:
+                    trace_gradient(it, gmax, succ, xk, xp, Jc, Jp)
                 if gmax <= 1e-10:
                     term = GRADIENT_TOL; break
                 if radius <= 1e-32:
                     term = MIN_RADIUS; break
                 it += 1
-                Jcs = Jc * sk[np.maximum(col_k[P.obs_kf], 0)][:, None, :]
+                # (no free keyframe observed: F == 0, Jc is all zero and there is no pose scale to gather)
+                Jcs = Jc * sk[np.maximum(col_k[P.obs_kf], 0)][:, None, :] if F else Jc
                 Jps = Jp * sp[col_p[P.obs_pt]][:, None, :]
                 if not reuse:
                     diag = (np.clip(_reduce(col_k[P.obs_kf][ok_k], (Jcs[ok_k] ** 2).sum(1), F), 1e-6, 1e32),
@@ -210,10 +239,15 @@ def solve(P: Problem, max_iterations=10, form="schur", mutants=(), trace=None):
                 ccost = _evaluate(ck, cp, P, mutants, jac=False)
                 if not np.isfinite(ccost):
                     ccost = np.finfo(float).max
-                if np.linalg.norm(flat(xk, xp) - flat(ck, cp)) <= 1e-8 * (x_norm + 1e-8):
+                step_norm = np.linalg.norm(flat(xk, xp) - flat(ck, cp))
+                if trace is not None:
+                    trace.append(("parameter", it, step_norm, parameter_tolerance * (x_norm + 1e-8), succ))
+                if step_norm <= parameter_tolerance * (x_norm + 1e-8):
                     term = PARAMETER_TOL; break
                 change = cost - ccost
-                if abs(change) <= 1e-6 * cost:
+                if trace is not None:
+                    trace.append(("function", it, abs(change), function_tolerance * cost, succ, cost))
+                if abs(change) <= function_tolerance * cost:
                     term = FUNCTION_TOL; break
                 rho = change / model_change
                 if trace is not None:
@@ -316,7 +350,8 @@ class World(Problem):
 
 
 def make_world(seed, n_free=4, n_fixed=4, n_points=200, f=500.0, noise_px=0.5, outlier_frac=0.05, pose_noise=(0.003, 0.01),
-               point_noise=0.02, once_frac=0.05, max_obs=6, zero_id=None, thresh=2.0):
+               point_noise=0.02, once_frac=0.05, max_obs=6, zero_id=None, thresh=2.0, all_free=False):
+    """all_free: every point is observed by ALL free keyframes (besides the constant ones it drew): the densest pair lists."""
     rng = np.random.default_rng(seed)
     K = n_free + n_fixed
     Tt = np.zeros((K, 3, 4))
@@ -336,6 +371,8 @@ def make_world(seed, n_free=4, n_fixed=4, n_points=200, f=500.0, noise_px=0.5, o
             m = int(rng.integers(2, min(max_obs, K) + 1))
             ks = [int(rng.integers(0, n_free))] + [int(k) for k in rng.choice(K, m, replace=False)]
             ks = list(dict.fromkeys(ks))
+        if all_free:
+            ks = list(range(n_free)) + [k for k in ks if k >= n_free]
         rng.shuffle(ks)                              # std::map<KeyFrame*> order: not keyframe order
         for k in ks:
             pc = Tt[k, :, :3] @ pts[q] + Tt[k, :, 3]
@@ -360,3 +397,16 @@ def make_world(seed, n_free=4, n_fixed=4, n_points=200, f=500.0, noise_px=0.5, o
     w = World(T0, const, p0, obs_kf, obs_pt, bearing, level, delta)
     w.fixed, w.kf_id, w.T_true, w.p_true, w.seed = fixed, kf_id, Tt, pts, seed
     return w
+
+
+def keep_observations(w, keep, levels=None):
+    """The world with the observations of the mask / index list `keep` only (keyframes and points stay, so some may lose
+    every observation), optionally with other levels. The arrays are copies: the source world is left as it is."""
+    keep = np.asarray(keep)
+    idx = np.nonzero(keep)[0] if keep.dtype == bool else keep.astype(np.int64)
+    lev = w.level if levels is None else np.asarray(levels, np.int64)
+    v = World(w.T.copy(), w.constant.copy(), w.points.copy(), w.obs_kf[idx], w.obs_pt[idx], w.bearing[idx], lev[idx], w.delta)
+    for k in ("fixed", "kf_id", "T_true", "p_true", "seed"):
+        if hasattr(w, k):
+            setattr(v, k, getattr(w, k))
+    return v
