@@ -142,6 +142,7 @@ EXPORTED_SYMBOLS = [
     "dsdtm_sparse_align_batch_sharded", "dsdtm_sparse_align_batch_streamed", "dsdtm_shard_range", "dsdtm_detect_cells_batch_device",
     "dsdtm_match_candidates_batch_device", "dsdtm_match_candidates_scratch_bytes", "dsdtm_track_frame",
     "dsdtm_track_frames", "dsdtm_local_ba", "dsdtm_local_ba_batch_device",
+    "dsdtm_frame_prefetch", "dsdtm_frame_wait", "dsdtm_track_frame_on", "dsdtm_frame_lift",
 ]
 
 
@@ -203,6 +204,15 @@ class TrackDesc(C.Structure):
                 ("obs_kf", C.c_void_p), ("obs_px", C.c_void_p), ("obs_level", C.c_void_p), ("obs_bearing", C.c_void_p),
                 ("mask", C.c_void_p), ("mask_stride", C.c_int32), ("cell_size", C.c_int32), ("max_pyr_levels", C.c_int32),
                 ("max_matches", C.c_int32), ("align2d_iters", C.c_int32), ("pose_opt", PoseOptParams)]
+
+
+class FrameImage(C.Structure):
+    """dsdtm_frame_image: what a frame is constructed from (gray image, optional 16-bit depth map) for dsdtm_frame_prefetch."""
+    _fields_ = [("gray", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("levels", C.c_int32),
+                ("depth", C.c_void_p), ("depth_stride", C.c_int32), ("depth_scale", C.c_float)]
+
+
+LIFT_MAX = 16384
 
 
 class TrackMatch(C.Structure):
@@ -346,6 +356,15 @@ def load(diag: bool | None = None):
     lib.dsdtm_track_frames.restype = C.c_int
     lib.dsdtm_track_frames.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.POINTER(TrackDesc), C.POINTER(TrackResult), C.c_void_p,
                                        C.c_void_p, C.c_void_p]
+    lib.dsdtm_frame_prefetch.restype = C.c_int
+    lib.dsdtm_frame_prefetch.argtypes = [C.c_void_p, C.POINTER(FrameImage), C.POINTER(C.c_void_p)]
+    lib.dsdtm_frame_wait.restype = C.c_int
+    lib.dsdtm_frame_wait.argtypes = [C.c_void_p, C.c_void_p]
+    lib.dsdtm_track_frame_on.restype = C.c_int
+    lib.dsdtm_track_frame_on.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(TrackDesc), C.c_void_p, C.POINTER(TrackResult),
+                                         C.c_void_p, C.c_void_p]
+    lib.dsdtm_frame_lift.restype = C.c_int
+    lib.dsdtm_frame_lift.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.dsdtm_shard_range.restype = None
     lib.dsdtm_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if diag:
@@ -414,6 +433,60 @@ class DeviceFrame:
         ctx.check(ctx.lib.dsdtm_frame_create_from_image(ctx.handle, img.ctypes.data_as(u8p), img.shape[1], img.shape[0],
                                                         img.strides[0], levels, C.byref(h)))
         return cls(ctx, h)
+
+    @classmethod
+    def prefetch(cls, ctx: "Context", gray, levels: int, depth=None, depth_scale: float = 5000.0):
+        """dsdtm_frame_prefetch: the frame is enqueued on the context's prefetch stream and the call returns at once.
+        `gray`: a 2-D uint8 array (rows may be padded) or a (pointer, width, height, stride) tuple for pinned / device memory;
+        `depth`: a 2-D uint16 array (rows may be padded), a (pointer, stride_in_elements) tuple, or None. An array in
+        pageable memory is staged before the call returns; anything else is read in place and must stay unchanged until
+        `.wait()` or the first call that uses the frame has returned (the frame keeps a reference to the arrays)."""
+        import numpy as np
+        im = FrameImage()
+        keep = []
+        if isinstance(gray, tuple):
+            ptr, w, h, stride = gray
+        else:
+            if gray.dtype != np.uint8 or gray.ndim != 2 or gray.strides[1] != 1:
+                gray = np.ascontiguousarray(gray, dtype=np.uint8)
+            keep.append(gray)
+            ptr, w, h, stride = gray.ctypes.data, gray.shape[1], gray.shape[0], gray.strides[0]
+        im.gray, im.width, im.height, im.stride, im.levels = ptr, w, h, stride, levels
+        if depth is not None:
+            if isinstance(depth, tuple):
+                im.depth, im.depth_stride = depth
+            else:
+                if depth.dtype != np.uint16 or depth.ndim != 2 or depth.strides[1] != 2 or depth.strides[0] % 2:
+                    depth = np.ascontiguousarray(depth, dtype=np.uint16)
+                if depth.shape != (h, w):
+                    raise ValueError(f"depth map {depth.shape} does not match the image {(h, w)}")
+                keep.append(depth)
+                im.depth, im.depth_stride = depth.ctypes.data, depth.strides[0] // 2
+            im.depth_scale = depth_scale
+        hnd = C.c_void_p()
+        ctx.check(ctx.lib.dsdtm_frame_prefetch(ctx.handle, C.byref(im), C.byref(hnd)))
+        df = cls(ctx, hnd)
+        df._keep = keep
+        return df
+
+    def wait(self):
+        """dsdtm_frame_wait: the host waits until the frame is resident (buffers read in place are the caller's again)."""
+        self.ctx.check(self.ctx.lib.dsdtm_frame_wait(self.ctx.handle, self.handle))
+        self._keep = []
+        return self
+
+    def lift(self, cam, T_c2w, px_xy):
+        """dsdtm_frame_lift: Frame::Get_FeatureDetph + Frame::UnProject for n pixels -> (depth[n] f32, -1 = none; p_world[n, 3])."""
+        import numpy as np
+        px = np.ascontiguousarray(px_xy, np.float32).reshape(-1, 2)
+        T = np.ascontiguousarray(np.asarray(T_c2w, np.float64).reshape(-1)[:12])
+        n = px.shape[0]
+        d = np.empty(n, np.float32)
+        p = np.empty((n, 3), np.float64)
+        c = cam if isinstance(cam, Camera) else camera_struct(cam)
+        self.ctx.check(self.ctx.lib.dsdtm_frame_lift(self.ctx.handle, self.handle, C.byref(c), T.ctypes.data, px.ctypes.data, n,
+                                                     d.ctypes.data, p.ctypes.data))
+        return d, p
 
     def close(self):
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):

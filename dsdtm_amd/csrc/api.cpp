@@ -99,7 +99,24 @@ struct dsdtm_ctx {
     void* h_lba = nullptr; size_t h_lba_cap = 0;
     hipEvent_t lba_event = nullptr; bool lba_recorded = false;
     hipEvent_t track_event = nullptr;     // dsdtm_track_frame: the local map has arrived (copied up on copy_stream[0] beside Run)
-    struct PooledFrame { size_t pitch; uint8_t* d; };
+    // dsdtm_frame_prefetch: a stream of its own, created on first use. Prefetched frames are numbered in the order they were
+    // enqueued on it; the stream runs in order, so "frame n is resident" implies every earlier one is. Event n % PREFETCH_EVENTS
+    // is recorded behind frame n (a wait on an event that a later frame has re-recorded waits a little longer, never too
+    // short). prefetch_settled: the highest number the HOST knows to be resident — frames up to it cost nothing more;
+    // prefetch_waiting: the highest number the context's stream has been told to wait for (hipStreamWaitEvent) — it becomes
+    // prefetch_settled at the next host synchronisation of that stream.
+    static constexpr int PREFETCH_EVENTS = 4;
+    hipStream_t prefetch_stream = nullptr;
+    hipEvent_t prefetch_event[PREFETCH_EVENTS] = {};
+    unsigned long long prefetch_seq = 0, prefetch_settled = 0, prefetch_waiting = 0;
+    // its own pinned staging ring (the context's staging block is busy with frame k while frame k + 1 is staged): a slot
+    // is written again only after the frame that used it last is resident
+    struct PrefetchSlot { void* h; size_t cap; unsigned long long seq; };
+    PrefetchSlot prefetch_slot[2] = {};
+    unsigned prefetch_next_slot = 0;
+    // (seq: the prefetch number of the destroyed frame — a buffer may go to the pool while its frame is still pending, and
+    // its next user's stream then waits for that frame's event, see frame_alloc)
+    struct PooledFrame { size_t pitch; uint8_t* d; unsigned long long seq; };
     static constexpr size_t FRAME_POOL = 8;
     std::vector<PooledFrame> frame_pool;
 };
@@ -289,7 +306,11 @@ void dsdtm_destroy(dsdtm_ctx* ctx) {
             if (g_live_ctx[i] == ctx) { g_live_ctx.erase(g_live_ctx.begin() + (long)i); break; }
     }
     (void)hipSetDevice(ctx->device);
+    if (ctx->prefetch_stream) (void)hipStreamSynchronize(ctx->prefetch_stream);   // a prefetch may be pending: nothing is freed under it
     if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); (void)hipStreamDestroy(ctx->stream); }
+    if (ctx->prefetch_stream) (void)hipStreamDestroy(ctx->prefetch_stream);
+    for (auto& e : ctx->prefetch_event) if (e) (void)hipEventDestroy(e);
+    for (auto& sl : ctx->prefetch_slot) if (sl.h) (void)hipHostFree(sl.h);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);
@@ -1009,6 +1030,10 @@ extern "C" int dsdtm_sparse_align_batch_streamed(dsdtm_ctx* const* ctx, int n_ct
 }
 
 // ---- host staging helpers ---------------------------------------------------------------
+// frames that dsdtm_frame_prefetch handed out and that may still be on their way (defined with the frames, below)
+static int frames_consume(dsdtm_ctx* ctx, unsigned long long seq, hipStream_t stream);
+static void frames_settle(dsdtm_ctx* ctx);
+
 struct PackedPyr {
     int levels;
     int w[DSDTM_MAX_LEVELS], h[DSDTM_MAX_LEVELS];
@@ -1047,8 +1072,9 @@ static int sparse_align_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
                             const dsdtm_camera* cam, const float* px_xy, const double* bearing,
                             const double* p_world, const uint8_t* initial, int n_features,
                             const double T_ref_w[12], double T_cur_w[12], const dsdtm_align_params* prm,
-                            int* n_tracked, dsdtm_align_stats* stats) {
+                            int* n_tracked, dsdtm_align_stats* stats, unsigned long long frames_seq = 0) {
     if (int rc = validate_params(ctx, prm, pl.levels)) return rc;
+    if (int rc = frames_consume(ctx, frames_seq, ctx->stream)) return rc;
     // Run() (:34-38): too few features -> 0, pose untouched. Decided on the host: no launch needed.
     if (stats) memset(stats, 0, sizeof *stats);
     *n_tracked = 0;
@@ -1118,6 +1144,7 @@ static int sparse_align_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
         if (int rc_launch = launch_batch(ctx, &b, cam, prm, ctx->stream, mode, &multi_cu)) return rc_launch;
         if (!zero_copy) HIP_TRY(ctx, hipMemcpyAsync(h + o_tc, d + o_tc, total - o_tc, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        frames_settle(ctx);
         if (!*h_flag) break;
         *h_flag = 0;
         if (!multi_cu || attempt == 1 || options().no_recover) {
@@ -1176,19 +1203,44 @@ struct dsdtm_frame {
     dsdtm_ctx* owner;    // compared only, never dereferenced through the frame (a frame may outlive its context)
     int device;
     uint8_t* d;          // packed pyramid (the layout of plan_pyramid), its own allocation or a place in `slab`
-    size_t pitch;
+    size_t pitch;        // of the packed pyramid
     PackedPyr pl;
     FrameSlab* slab = nullptr;
+    size_t bytes = 0;    // of its own allocation (the pool's size key): the pyramid and, behind it, the depth plane
+    float* depth = nullptr;          // pl.w[0] x pl.h[0] floats, metres (dsdtm_frame_prefetch with a depth map), inside the allocation
+    unsigned long long seq = 0;      // dsdtm_frame_prefetch: the frame's number on the prefetch stream; 0: never pending
 };
+// tests/test_frame_prefetch_gpu.py reads a frame's pyramid back through these first members (it has no public entry to do so):
+// a change of their layout must fail here, not there
+static_assert(offsetof(dsdtm_frame, owner) == 0 && offsetof(dsdtm_frame, device) == 8 && offsetof(dsdtm_frame, d) == 16 &&
+              offsetof(dsdtm_frame, pitch) == 24, "struct dsdtm_frame: update _FrameHead in tests/test_frame_prefetch_gpu.py");
+
+// A frame that dsdtm_frame_prefetch handed out may still be on its way: before `stream` reads frames numbered up to `seq`
+// it waits for the event behind that number — on the device, never on the host. Nothing to do once the host knows the
+// frame to be resident (prefetch_settled), or when the context's stream has already been told to wait that far.
+static int frames_consume(dsdtm_ctx* ctx, unsigned long long seq, hipStream_t stream) {
+    if (seq <= ctx->prefetch_settled || stream == ctx->prefetch_stream) return DSDTM_OK;
+    if (stream == ctx->stream && seq <= ctx->prefetch_waiting) return DSDTM_OK;
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->prefetch_event[seq % dsdtm_ctx::PREFETCH_EVENTS], 0));
+    if (stream == ctx->stream) ctx->prefetch_waiting = seq;
+    return DSDTM_OK;
+}
+// behind a host synchronisation of the context's stream: what it was told to wait for has arrived.
+// INVARIANT: called only after hipStreamSynchronize(ctx->stream) has returned success — never behind a wait for another
+// stream or for an event: prefetch_waiting counts the waits enqueued on ctx->stream alone (frames_consume).
+static void frames_settle(dsdtm_ctx* ctx) {
+    if (ctx->prefetch_waiting > ctx->prefetch_settled) ctx->prefetch_settled = ctx->prefetch_waiting;
+}
 
 // The frame pool is shared with dsdtm_frame_destroy, which may run on any thread (a garbage collector's): it is touched only
 // under g_live_mutex, held across the liveness check of the context — dsdtm_destroy takes a context off the live list under
 // the same lock before it frees the pool.
-static uint8_t* pool_take(dsdtm_ctx* ctx, size_t bytes) {
+static uint8_t* pool_take(dsdtm_ctx* ctx, size_t bytes, unsigned long long* seq) {
     std::lock_guard<std::mutex> g(g_live_mutex);
     for (size_t i = 0; i < ctx->frame_pool.size(); ++i)
         if (ctx->frame_pool[i].pitch == bytes) {                // a destroyed frame's buffer of this size (its users have drained:
             uint8_t* d = ctx->frame_pool[i].d;                  // every entry that takes a dsdtm_frame waits for its stream)
+            *seq = ctx->frame_pool[i].seq;                      // (its prefetch may not have: the next user waits for that)
             ctx->frame_pool.erase(ctx->frame_pool.begin() + (long)i);
             return d;
         }
@@ -1197,24 +1249,35 @@ static uint8_t* pool_take(dsdtm_ctx* ctx, size_t bytes) {
 
 // its own, LIVE context on the same device: the buffer goes to that context's pool (no hipFree, which would wait for the whole
 // device); false: the caller frees it
-static bool pool_give(dsdtm_ctx* ctx, dsdtm_ctx* owner, int device, uint8_t* d, size_t bytes) {
+static bool pool_give(dsdtm_ctx* ctx, dsdtm_ctx* owner, int device, uint8_t* d, size_t bytes, unsigned long long seq = 0) {
     if (!ctx || !d || owner != ctx) return false;
     std::lock_guard<std::mutex> g(g_live_mutex);
     if (!ctx_is_live_locked(ctx) || ctx->device != device || ctx->frame_pool.size() >= dsdtm_ctx::FRAME_POOL) return false;
-    try { ctx->frame_pool.push_back(dsdtm_ctx::PooledFrame{bytes, d}); } catch (...) { return false; }
+    try { ctx->frame_pool.push_back(dsdtm_ctx::PooledFrame{bytes, d, seq}); } catch (...) { return false; }
     return true;
 }
 
-static int frame_alloc(dsdtm_ctx* ctx, const PackedPyr& pl, dsdtm_frame** out) {
+// `stream`: the stream that will write the new frame. with_depth: room for the float depth plane behind the pyramid.
+static int frame_alloc(dsdtm_ctx* ctx, const PackedPyr& pl, hipStream_t stream, dsdtm_frame** out, bool with_depth = false) {
     dsdtm_frame* f = new (std::nothrow) dsdtm_frame();
     if (!f) return DSDTM_ERR_NOMEM;
-    f->owner = ctx; f->device = ctx->device; f->pl = pl; f->pitch = align_up(pl.bytes, 256); f->d = pool_take(ctx, f->pitch);
-    if (f->d) { *out = f; return DSDTM_OK; }
-    if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&f->d, f->pitch) != hipSuccess) {
-        set_err(ctx, "hipMalloc of a %zu-byte frame failed", f->pitch);
+    f->owner = ctx; f->device = ctx->device; f->pl = pl; f->pitch = align_up(pl.bytes, 256);
+    f->bytes = f->pitch + (with_depth ? align_up((size_t)pl.w[0] * pl.h[0] * sizeof(float), 256) : 0);
+    unsigned long long pooled_seq = 0;
+    f->d = pool_take(ctx, f->bytes, &pooled_seq);
+    if (f->d) {
+        // the buffer of a frame that was destroyed while its prefetch was pending: that prefetch still writes it
+        if (int rc = frames_consume(ctx, pooled_seq, stream)) {
+            if (!pool_give(ctx, ctx, ctx->device, f->d, f->bytes, pooled_seq)) (void)hipFree(f->d);
+            delete f;
+            return rc;
+        }
+    } else if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&f->d, f->bytes) != hipSuccess) {
+        set_err(ctx, "hipMalloc of a %zu-byte frame failed", f->bytes);
         delete f;
         return DSDTM_ERR_NOMEM;
     }
+    if (with_depth) f->depth = (float*)(f->d + f->pitch);
     *out = f;
     return DSDTM_OK;
 }
@@ -1226,11 +1289,12 @@ extern "C" int dsdtm_frame_create(dsdtm_ctx* ctx, const dsdtm_pyramid* pyr, dsdt
     if (int rc = plan_pyramid(ctx, pyr, &pl)) return rc;
     if (int rc = ensure_stage(ctx, pl.bytes)) return rc;
     dsdtm_frame* f = nullptr;
-    if (int rc = frame_alloc(ctx, pl, &f)) return rc;
+    if (int rc = frame_alloc(ctx, pl, ctx->stream, &f)) return rc;
     pack_pyramid(pyr, pl, (uint8_t*)ctx->h_pinned);
     hipError_t e = hipMemcpyAsync(f->d, ctx->h_pinned, pl.bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // the pinned buffer is reused by the next call
     if (e != hipSuccess) { set_err(ctx, "frame upload failed: %s", hipGetErrorString(e)); dsdtm_frame_destroy(ctx, f); return DSDTM_ERR_HIP; }
+    frames_settle(ctx);
     *out = f;
     return DSDTM_OK;
 }
@@ -1253,7 +1317,7 @@ extern "C" int dsdtm_frame_create_from_image(dsdtm_ctx* ctx, const uint8_t* leve
     pl.bytes = o;
     if (int rc = ensure_stage(ctx, (size_t)width * height)) return rc;
     dsdtm_frame* f = nullptr;
-    if (int rc = frame_alloc(ctx, pl, &f)) return rc;
+    if (int rc = frame_alloc(ctx, pl, ctx->stream, &f)) return rc;
     uint8_t* hp = (uint8_t*)ctx->h_pinned;
     if (stride == width) memcpy(hp, level0, (size_t)width * height);
     else for (int y = 0; y < height; ++y) memcpy(hp + (size_t)y * width, level0 + (size_t)y * stride, width);
@@ -1270,6 +1334,7 @@ extern "C" int dsdtm_frame_create_from_image(dsdtm_ctx* ctx, const uint8_t* leve
         dsdtm_frame_destroy(ctx, f);
         return rc;
     }
+    frames_settle(ctx);
     *out = f;
     return DSDTM_OK;
 }
@@ -1283,10 +1348,210 @@ extern "C" void dsdtm_frame_destroy(dsdtm_ctx* ctx, dsdtm_frame* f) {
         delete sl;
         return;
     }
-    if (pool_give(ctx, f->owner, f->device, f->d, f->pitch)) { delete f; return; }
+    // (a frame whose prefetch is still pending: the buffer goes to the pool with the frame's number, and its next user's
+    // stream waits for the event behind it — frame_alloc)
+    if (pool_give(ctx, f->owner, f->device, f->d, f->bytes, f->seq)) { delete f; return; }
     (void)hipSetDevice(f->device);
     if (f->d) (void)hipFree(f->d);       // hipFree waits for the device's pending work
     delete f;
+}
+
+// ---- RGB-D frames that enter the device ahead of time --------------------------------------------------------------
+// rgbd.hip defines these; weak here, as the local-BA launches below, so that a host-only build of this file without the
+// kernels still links. The entry points test them and fail cleanly where they are missing.
+namespace dsdtm {
+__attribute__((weak)) hipError_t depth_ingest_launch(const uint16_t* src, int src_stride, float* dst, int w, int h, float inv_scale,
+                                                     int num_cus, hipStream_t stream);
+__attribute__((weak)) hipError_t lift_launch(const LiftArgs& args, hipStream_t stream);
+}
+
+// Where an image of the caller lives, as dsdtm_track_frame sorts it (0: ordinary host memory, 1: pinned host memory,
+// 2: this device's memory; -1: another device's).
+static int image_memory(dsdtm_ctx* ctx, const void* p) {
+    hipPointerAttribute_t pa_;
+    if (hipPointerGetAttributes(&pa_, p) != hipSuccess) { (void)hipGetLastError(); return 0; }    // (an ordinary host pointer: not an error)
+    if (pa_.type == hipMemoryTypeDevice) return pa_.device == ctx->device ? 2 : -1;
+    return pa_.type == hipMemoryTypeHost ? 1 : 0;
+}
+
+// Frame construction (src/Frame.cpp:35-41) off the tracked frame's chain: level 0, the pyramid and the depth conversion are
+// enqueued on the context's prefetch stream, an event is recorded behind them and the call returns.
+extern "C" int dsdtm_frame_prefetch(dsdtm_ctx* ctx, const dsdtm_frame_image* im, dsdtm_frame** out) {
+    if (!ctx) return DSDTM_ERR_INVALID;
+    if (!out) { set_err(ctx, "prefetch: out is NULL"); return DSDTM_ERR_INVALID; }
+    *out = nullptr;
+    if (!im) { set_err(ctx, "prefetch: image is NULL"); return DSDTM_ERR_INVALID; }
+    if (!im->gray) { set_err(ctx, "prefetch: image->gray is NULL"); return DSDTM_ERR_INVALID; }
+    if (im->width <= 0 || im->height <= 0 || im->stride < im->width || im->levels <= 0 || im->levels > DSDTM_MAX_LEVELS ||
+        im->width > 16384 || im->height > 16384) {
+        set_err(ctx, "prefetch: bad image geometry (width %d, height %d, stride %d, levels %d)", im->width, im->height, im->stride, im->levels);
+        return DSDTM_ERR_INVALID;
+    }
+    if (im->depth && (im->depth_stride < im->width || !(im->depth_scale > 0.0f))) {
+        set_err(ctx, "prefetch: bad depth map (depth_stride %d < width %d, or depth_scale %g not positive)", im->depth_stride, im->width, (double)im->depth_scale);
+        return DSDTM_ERR_INVALID;
+    }
+    if (im->depth && !depth_ingest_launch) { set_err(ctx, "prefetch: this build has no depth kernels"); return DSDTM_ERR_INVALID; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    {
+        // (the call allocates, waits for events and records one on a stream of its own: none of that can be part of a capture)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+        if (cs != hipStreamCaptureStatusNone) { set_err(ctx, "prefetch: not inside a stream capture"); return DSDTM_ERR_INVALID; }
+    }
+    const int gray_mem = image_memory(ctx, im->gray), depth_mem = im->depth ? image_memory(ctx, im->depth) : 0;
+    if (gray_mem < 0 || depth_mem < 0) { set_err(ctx, "prefetch: image->%s lives on another device than the context's (%d)", gray_mem < 0 ? "gray" : "depth", ctx->device); return DSDTM_ERR_INVALID; }
+    if (!ctx->prefetch_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->prefetch_stream, hipStreamNonBlocking));
+    for (auto& e : ctx->prefetch_event) if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    hipStream_t ps = ctx->prefetch_stream;
+
+    PackedPyr pl;
+    int st[DSDTM_MAX_LEVELS];
+    pl.levels = im->levels;
+    {
+        size_t o = 0;
+        for (int l = 0; l < pl.levels; ++l) {
+            pl.w[l] = l ? (pl.w[l - 1] + 1) / 2 : im->width; pl.h[l] = l ? (pl.h[l - 1] + 1) / 2 : im->height; st[l] = pl.w[l];
+            pl.off[l] = o; o += align_up((size_t)pl.w[l] * pl.h[l], 64);
+        }
+        pl.bytes = o;
+    }
+    const size_t W = (size_t)im->width, H = (size_t)im->height, img = W * H;
+    // how each image travels (the gray image as in dsdtm_track_frame): read in place by a kernel, moved by the copy engine
+    // from where it is, or staged — copied into a slot of the prefetch ring now, so that the caller's buffer is free on return
+    const bool contiguous = im->stride == im->width, aligned = !(((size_t)im->gray) & 15);
+    const void* gray_dev = nullptr;                          // the gray image as a kernel sees it, where a kernel reads it in place
+    bool gray_staged = false;
+    if (gray_mem == 2) { if (contiguous && aligned) gray_dev = im->gray; }
+    else if (gray_mem == 1 && contiguous) {
+        void* p_ = nullptr;
+        if (aligned && hipHostGetDevicePointer(&p_, (void*)im->gray, 0) == hipSuccess) gray_dev = p_;
+        else (void)hipGetLastError();
+    } else gray_staged = true;
+    const uint16_t* depth_dev = nullptr;                     // the depth map as the kernel sees it
+    int depth_dev_stride = im->depth_stride;
+    bool depth_staged = false;
+    if (im->depth) {
+        if (depth_mem == 2) depth_dev = im->depth;
+        else if (depth_mem == 1) {
+            void* p_ = nullptr;
+            if (hipHostGetDevicePointer(&p_, (void*)im->depth, 0) == hipSuccess) depth_dev = (const uint16_t*)p_;
+            else { (void)hipGetLastError(); depth_staged = true; }
+        } else depth_staged = true;
+    }
+    const size_t s_gray = 0, s_depth = gray_staged ? align_up(img, 256) : 0;
+    const size_t stage_bytes = s_depth + (depth_staged ? img * sizeof(uint16_t) : 0);
+    dsdtm_ctx::PrefetchSlot* slot = nullptr;
+    if (stage_bytes) {
+        slot = &ctx->prefetch_slot[ctx->prefetch_next_slot & 1u];
+        // the frame that used this slot last may still be reading it
+        if (slot->seq > ctx->prefetch_settled) {
+            HIP_TRY(ctx, hipEventSynchronize(ctx->prefetch_event[slot->seq % dsdtm_ctx::PREFETCH_EVENTS]));
+            ctx->prefetch_settled = slot->seq;
+        }
+        if (stage_bytes > slot->cap) {
+            if (slot->h) (void)hipHostFree(slot->h);
+            slot->h = nullptr; slot->cap = 0;
+            const size_t cap = align_up(stage_bytes + stage_bytes / 4, 1 << 16);
+            HIP_TRY(ctx, hipHostMalloc(&slot->h, cap, hipHostMallocDefault));
+            slot->cap = cap;
+        }
+    }
+    dsdtm_frame* f = nullptr;
+    if (int rc = frame_alloc(ctx, pl, ps, &f, im->depth != nullptr)) return rc;
+    // on any failure: no frame, nothing pending (what was enqueued is waited for), the slot and the numbering untouched
+    auto fail = [&](int rc) {
+        (void)hipStreamSynchronize(ps);
+        dsdtm_frame_destroy(ctx, f);
+        return rc;
+    };
+#define PREFETCH_TRY(call)                                                                                     \
+    do {                                                                                                       \
+        hipError_t e_ = (call);                                                                                \
+        if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
+    } while (0)
+    uint8_t* sh = slot ? (uint8_t*)slot->h : nullptr;
+    uint8_t* shd = nullptr;                                  // the slot as the device sees it
+    if (slot) { void* p_ = nullptr; PREFETCH_TRY(hipHostGetDevicePointer(&p_, slot->h, 0)); shd = (uint8_t*)p_; }
+    if (gray_staged) {
+        if (contiguous) memcpy(sh + s_gray, im->gray, img);
+        else for (size_t y = 0; y < H; ++y) memcpy(sh + s_gray + y * W, im->gray + y * (size_t)im->stride, W);
+        gray_dev = shd + s_gray;
+    }
+    if (depth_staged) {
+        uint16_t* dd = (uint16_t*)(sh + s_depth);
+        if (im->depth_stride == im->width) memcpy(dd, im->depth, img * sizeof(uint16_t));
+        else for (size_t y = 0; y < H; ++y) memcpy(dd + y * W, im->depth + y * (size_t)im->depth_stride, W * sizeof(uint16_t));
+        depth_dev = (const uint16_t*)(shd + s_depth); depth_dev_stride = im->width;
+    }
+    // level 0 by a kernel where a kernel can read it (ingest_kernel, pyrdown.hip), else by the copy engine (a pinned image
+    // at an odd address or one the device cannot address; a strided or odd device image), then the pyramid
+    if (gray_dev) PREFETCH_TRY(ingest_launch(gray_dev, f->d, img, nullptr, nullptr, 0, ps));
+    else if (gray_mem == 2) PREFETCH_TRY(hipMemcpy2DAsync(f->d, W, im->gray, (size_t)im->stride, W, H, hipMemcpyDeviceToDevice, ps));
+    else PREFETCH_TRY(hipMemcpyAsync(f->d, im->gray, img, hipMemcpyHostToDevice, ps));
+    if (int rc = dsdtm_pyrdown_batch_device(ctx, f->d, f->pitch, 1, pl.levels, pl.w, pl.h, st, pl.off, ps)) return fail(rc);
+    if (im->depth) PREFETCH_TRY(depth_ingest_launch(depth_dev, depth_dev_stride, f->depth, im->width, im->height, 1.0f / im->depth_scale, ctx->num_cus, ps));
+    const unsigned long long seq = ctx->prefetch_seq + 1;
+    PREFETCH_TRY(hipEventRecord(ctx->prefetch_event[seq % dsdtm_ctx::PREFETCH_EVENTS], ps));
+#undef PREFETCH_TRY
+    ctx->prefetch_seq = seq;
+    f->seq = seq;
+    if (slot) { slot->seq = seq; ctx->prefetch_next_slot += 1; }
+    *out = f;
+    return DSDTM_OK;
+}
+
+extern "C" int dsdtm_frame_wait(dsdtm_ctx* ctx, const dsdtm_frame* f) {
+    if (!ctx) return DSDTM_ERR_INVALID;
+    if (!f) { set_err(ctx, "frame_wait: frame is NULL"); return DSDTM_ERR_INVALID; }
+    if (f->owner != ctx) { set_err(ctx, "frame belongs to another context"); return DSDTM_ERR_INVALID; }
+    if (f->seq <= ctx->prefetch_settled) return DSDTM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->prefetch_event[f->seq % dsdtm_ctx::PREFETCH_EVENTS]));
+    ctx->prefetch_settled = f->seq;
+    return DSDTM_OK;
+}
+
+// Frame::Get_FeatureDetph(cv::Point2f) + Frame::UnProject (src/Frame.cpp:152-157, 201-224) for n pixels of a resident frame.
+extern "C" int dsdtm_frame_lift(dsdtm_ctx* ctx, const dsdtm_frame* f, const dsdtm_camera* cam, const double* T_c2w,
+                                const float* px_xy, int n, float* depth_out, double* p_world_out) {
+    if (!ctx) return DSDTM_ERR_INVALID;
+    if (!f) { set_err(ctx, "lift: frame is NULL"); return DSDTM_ERR_INVALID; }
+    if (!cam) { set_err(ctx, "lift: cam is NULL"); return DSDTM_ERR_INVALID; }
+    if (!T_c2w) { set_err(ctx, "lift: T_c2w is NULL"); return DSDTM_ERR_INVALID; }
+    if (n < 0 || n > DSDTM_LIFT_MAX) { set_err(ctx, "lift: n = %d outside 0..%d", n, DSDTM_LIFT_MAX); return DSDTM_ERR_INVALID; }
+    if (n > 0 && (!px_xy || !depth_out || !p_world_out)) {
+        set_err(ctx, "lift: %s is NULL", !px_xy ? "px_xy" : !depth_out ? "depth_out" : "p_world_out"); return DSDTM_ERR_INVALID;
+    }
+    if (f->owner != ctx) { set_err(ctx, "frame belongs to another context"); return DSDTM_ERR_INVALID; }
+    if (!f->depth) { set_err(ctx, "lift: the frame has no depth map (dsdtm_frame_image.depth was NULL)"); return DSDTM_ERR_INVALID; }
+    if (!lift_launch) { set_err(ctx, "lift: this build has no depth kernels"); return DSDTM_ERR_INVALID; }
+    if (n == 0) return DSDTM_OK;
+    const size_t N = (size_t)n;
+    size_t o = 0;
+    const size_t o_px = o; o += align_up(N * 8, 256);
+    const size_t o_d = o; o += align_up(N * 4, 256);
+    const size_t o_p = o; o += align_up(N * 24, 256);
+    if (int rc = ensure_stage(ctx, o)) return rc;
+    uint8_t* h = (uint8_t*)ctx->h_pinned;
+    void* hd_ = nullptr;
+    HIP_TRY(ctx, hipHostGetDevicePointer(&hd_, ctx->h_pinned, 0));
+    uint8_t* hd = (uint8_t*)hd_;
+    memcpy(h + o_px, px_xy, N * 8);
+    // every input is read once and every result written once: straight from / to the pinned block
+    LiftArgs a;
+    memset(&a, 0, sizeof a);
+    a.depth = f->depth; a.w = f->pl.w[0]; a.h = f->pl.h[0];
+    a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
+    memcpy(a.T, T_c2w, 96);
+    a.px_xy = (const float*)(hd + o_px); a.depth_out = (float*)(hd + o_d); a.p_world = (double*)(hd + o_p); a.n = n;
+    if (int rc = frames_consume(ctx, f->seq, ctx->stream)) return rc;
+    HIP_TRY(ctx, lift_launch(a, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    frames_settle(ctx);
+    memcpy(depth_out, h + o_d, N * 4);
+    memcpy(p_world_out, h + o_p, N * 24);
+    return DSDTM_OK;
 }
 
 extern "C" int dsdtm_sparse_align_frames(dsdtm_ctx* ctx, const dsdtm_frame* ref, const dsdtm_frame* cur,
@@ -1304,13 +1569,13 @@ extern "C" int dsdtm_sparse_align_frames(dsdtm_ctx* ctx, const dsdtm_frame* ref,
     for (int l = 0; l < ref->pl.levels; ++l)
         if (ref->pl.w[l] != cur->pl.w[l] || ref->pl.h[l] != cur->pl.h[l]) { set_err(ctx, "ref/cur level %d differ in size", l); return DSDTM_ERR_INVALID; }
     return sparse_align_one(ctx, ref->pl, nullptr, nullptr, ref->d, cur->d, ref->pitch, cam, px_xy, bearing, p_world, initial,
-                            n_features, T_ref_w, T_cur_w, prm, n_tracked, stats);
+                            n_features, T_ref_w, T_cur_w, prm, n_tracked, stats, ref->seq > cur->seq ? ref->seq : cur->seq);
 }
 
 // ---- feature detector (per-cell part) ----------------------------------------------------------
 static int detect_cells_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyramid* host_pyr, const uint8_t* dev_pyr,
                             const uint8_t* grid_occupied, const dsdtm_detect_params* prm, float* cell_score,
-                            int32_t* cell_x, int32_t* cell_y, int32_t* cell_level) {
+                            int32_t* cell_x, int32_t* cell_y, int32_t* cell_level, unsigned long long frame_seq = 0) {
     if (!prm || !cell_score || !cell_x || !cell_y || !cell_level) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
     if (prm->cell_size <= 0 || prm->grid_cols <= 0 || prm->grid_rows <= 0 || prm->levels <= 0 || prm->levels > pl.levels ||
         prm->barrier < 0 || prm->barrier > 254 || !(prm->detection_threshold >= 0.0f) ||
@@ -1333,6 +1598,7 @@ static int detect_cells_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
     uint8_t* d = (uint8_t*)ctx->d_stage;
     if (!dev_pyr) pack_pyramid(host_pyr, pl, h + o_pyr);
     if (grid_occupied) memcpy(h + o_occ, grid_occupied, G); else memset(h + o_occ, 0, G);
+    if (int rc = frames_consume(ctx, frame_seq, ctx->stream)) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d + o_key, 0, G * 8, ctx->stream));
     DetectArgs a;
@@ -1346,6 +1612,7 @@ static int detect_cells_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
     HIP_TRY(ctx, detect_launch(a, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(h + o_key, d + o_key, G * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    frames_settle(ctx);
     const unsigned long long* keys = (const unsigned long long*)(h + o_key);
     for (size_t k = 0; k < G; ++k) {
         if (!keys[k]) { cell_score[k] = prm->detection_threshold; cell_x[k] = 0; cell_y[k] = 0; cell_level[k] = 0; continue; }   // :74
@@ -1372,7 +1639,7 @@ extern "C" int dsdtm_detect_cells_frame(dsdtm_ctx* ctx, const dsdtm_frame* frame
     if (!ctx) return DSDTM_ERR_INVALID;
     if (!frame) { set_err(ctx, "NULL frame"); return DSDTM_ERR_INVALID; }
     if (frame->owner != ctx) { set_err(ctx, "frame belongs to another context"); return DSDTM_ERR_INVALID; }
-    return detect_cells_one(ctx, frame->pl, nullptr, frame->d, grid_occupied, prm, cell_score, cell_x, cell_y, cell_level);
+    return detect_cells_one(ctx, frame->pl, nullptr, frame->d, grid_occupied, prm, cell_score, cell_x, cell_y, cell_level, frame->seq);
 }
 
 // The image part of Feature_detector::detect for n_frames packed device pyramids in one go (independent sequences,
@@ -1665,8 +1932,10 @@ extern "C" int dsdtm_match_candidates_frames(dsdtm_ctx* ctx, const dsdtm_frame* 
     if (m == 0) return DSDTM_OK;
     if (cur->owner != ctx) { set_err(ctx, "frame belongs to another context"); return DSDTM_ERR_INVALID; }
     const PackedPyr& p0 = cur->pl;
+    unsigned long long frames_seq = cur->seq;
     for (int k = 0; k < n_kf; ++k) {
         if (!kf[k] || kf[k]->owner != ctx) { set_err(ctx, "keyframe %d: NULL or foreign frame", k); return DSDTM_ERR_INVALID; }
+        if (kf[k]->seq > frames_seq) frames_seq = kf[k]->seq;
         const PackedPyr& pk = kf[k]->pl;
         if (pk.levels != p0.levels || memcmp(pk.w, p0.w, sizeof(int) * p0.levels) || memcmp(pk.h, p0.h, sizeof(int) * p0.levels)) {
             set_err(ctx, "keyframe %d pyramid geometry differs from the current frame", k); return DSDTM_ERR_INVALID;
@@ -1707,6 +1976,7 @@ extern "C" int dsdtm_match_candidates_frames(dsdtm_ctx* ctx, const dsdtm_frame* 
     memcpy(h + o_rl, ref_level, M * 4);
     memcpy(h + o_rp, ref_px, M * 8);
     memcpy(h + o_px, px_xy, M * 16);
+    if (int rc = frames_consume(ctx, frames_seq, ctx->stream)) return rc;
     // Every input is read once per candidate and every result written once: the two kernels take them straight
     // from / to the pinned block (no copy operations around the launches); only the warped patches, which the
     // second kernel re-reads at every iteration, live in device memory.
@@ -1748,6 +2018,7 @@ extern "C" int dsdtm_match_candidates_frames(dsdtm_ctx* ctx, const dsdtm_frame* 
     }
     if (!zero_copy) HIP_TRY(ctx, hipMemcpyAsync(h + o_px, d + o_px, out_end - o_px, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    frames_settle(ctx);
     memcpy(px_xy, h + o_px, M * 16);
     memcpy(search_level, h + o_sl, M * 4);
     memcpy(converged, h + o_cv, M);
@@ -2083,9 +2354,12 @@ struct TrackPlan {
     PackedPyr pl;
     int st[DSDTM_MAX_LEVELS];
     int nnz, max_search_level, grid_rows, grid_cols;
+    unsigned long long frames_seq;   // the latest prefetch number among the reference frame and the keyframes (frames_consume)
 };
-static int track_check_desc(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, TrackPlan* out) {
-    if (!d->image || d->width <= 0 || d->height <= 0 || d->stride < d->width || d->levels <= 0 || d->levels > DSDTM_MAX_LEVELS ||
+// resident: the descriptor of dsdtm_track_frame_on — the new frame is already on the device and `image` must be NULL
+static int track_check_desc(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, TrackPlan* out, bool resident = false) {
+    if (resident && d->image) { set_err(ctx, "track_frame_on: desc->image must be NULL (the frame is already on the device)"); return DSDTM_ERR_INVALID; }
+    if ((!resident && (!d->image || d->stride < d->width)) || d->width <= 0 || d->height <= 0 || d->levels <= 0 || d->levels > DSDTM_MAX_LEVELS ||
         d->width > 16384 || d->height > 16384) { set_err(ctx, "track: bad image geometry"); return DSDTM_ERR_INVALID; }
     // the grid, the packed mask (stride d->width) and the pyramid are sized by the image, the reprojection is bounded by the
     // camera: a camera of another size would read the mask out of bounds (larger) or drop points silently (smaller)
@@ -2129,6 +2403,8 @@ static int track_check_desc(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
     const int M = d->n_points;
     const int nnz = M > 0 ? d->obs_offset[M] : 0;
     out->nnz = nnz; out->max_search_level = max_search_level;
+    out->frames_seq = d->ref->seq;
+    for (int k = 0; k < d->n_kf; ++k) if (d->kf[k]->seq > out->frames_seq) out->frames_seq = d->kf[k]->seq;
     if (M > 0) {
         if (d->obs_offset[0] != 0 || nnz < 0 || (nnz > 0 && (!d->obs_kf || !d->obs_px || !d->obs_level || !d->obs_bearing))) {
             set_err(ctx, "track: bad observation arrays"); return DSDTM_ERR_INVALID;
@@ -2155,13 +2431,31 @@ static int track_check_desc(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
 // waits once. What crosses the link crosses it once and off the kernels' critical paths: level 0 and Run's inputs are read from
 // host-mapped pinned memory by ONE kernel into HBM, the local map goes up on a second stream while Run runs, every later kernel
 // works on device memory and the few results are written (posted) to the pinned block by whichever kernel has them first.
-extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, dsdtm_track_result* res,
-                                 dsdtm_track_match* matches, double* residual_norm) {
-    if (!ctx) return DSDTM_ERR_INVALID;
-    if (!cam || !d || !res || !matches || !residual_norm) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
+// cur == NULL: dsdtm_track_frame — the new frame is made here from d->image. cur != NULL: dsdtm_track_frame_on — the frame is
+// already on the device (or on its way there: the stream waits for its event); the chain starts at Run.
+static int track_frame_impl(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, dsdtm_frame* cur, dsdtm_track_result* res,
+                            dsdtm_track_match* matches, double* residual_norm) {
     memset(res, 0, sizeof *res);
     TrackPlan plan;
-    if (int rc = track_check_desc(ctx, cam, d, &plan)) return rc;
+    if (cur) {
+        if (cur->owner != ctx) { set_err(ctx, "track_frame_on: cur belongs to another context"); return DSDTM_ERR_INVALID; }
+        if (d->image) { set_err(ctx, "track_frame_on: desc->image must be NULL (the frame is already on the device)"); return DSDTM_ERR_INVALID; }
+        if (cur->pl.levels != d->levels || cur->pl.w[0] != d->width || cur->pl.h[0] != d->height) {
+            set_err(ctx, "track_frame_on: desc->width / height / levels (%dx%d, %d) are not the frame's (%dx%d, %d)", d->width, d->height,
+                    d->levels, cur->pl.w[0], cur->pl.h[0], cur->pl.levels);
+            return DSDTM_ERR_INVALID;
+        }
+    }
+    if (int rc = track_check_desc(ctx, cam, d, &plan, cur != nullptr)) return rc;
+    if (cur) {
+        const PackedPyr& q = cur->pl;
+        if (memcmp(q.w, plan.pl.w, sizeof(int) * q.levels) || memcmp(q.h, plan.pl.h, sizeof(int) * q.levels)) {   // (a frame from dsdtm_frame_create with levels of its own)
+            set_err(ctx, "track_frame_on: desc->width / height / levels (%dx%d, %d) are not the frame's (%dx%d, %d)", d->width, d->height,
+                    d->levels, q.w[0], q.h[0], q.levels);
+            return DSDTM_ERR_INVALID;
+        }
+        if (cur->seq > plan.frames_seq) plan.frames_seq = cur->seq;
+    }
     const PackedPyr& pl = plan.pl;
     const int* st = plan.st;
     const int max_search_level = plan.max_search_level, M = d->n_points, nnz = plan.nnz;
@@ -2201,12 +2495,12 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
     uint8_t* hd = (uint8_t*)hd_;                       // the pinned block as the device sees it
     hipStream_t stream = ctx->stream;
 
-    dsdtm_frame* f = nullptr;
-    if (int rc = frame_alloc(ctx, pl, &f)) return rc;
+    dsdtm_frame* f = cur;
+    if (!cur) { if (int rc = frame_alloc(ctx, pl, stream, &f)) return rc; }
     auto fail = [&](int rc) {
         if (ctx->copy_stream[0]) (void)hipStreamSynchronize(ctx->copy_stream[0]);
         (void)hipStreamSynchronize(stream);
-        dsdtm_frame_destroy(ctx, f);
+        if (!cur) dsdtm_frame_destroy(ctx, f);          // (a frame the caller handed in stays the caller's)
         return rc;
     };
 #define TRACK_TRY(call)                                                                                        \
@@ -2224,7 +2518,7 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
     // (an image that already lives in this device's memory — a capture or decode pipeline on the GPU — is read from there by the same
     // kernel, or by a device-to-device copy when it is strided or not 16-byte aligned)
     bool pinned_image = false, device_image = false;
-    {
+    if (!cur) {
         hipPointerAttribute_t pa_;
         if (hipPointerGetAttributes(&pa_, d->image) == hipSuccess) {
             device_image = pa_.type == hipMemoryTypeDevice;
@@ -2233,14 +2527,16 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
         } else (void)hipGetLastError();                // (an ordinary host pointer: not an error)
     }
     const void* img_dev = nullptr;                     // the image as the device sees it
-    if (device_image) {
+    if (cur) {
+        // (nothing to bring in: the frame is resident, or its prefetch is what the stream waits for below)
+    } else if (device_image) {
         if (d->stride == d->width && !(((size_t)d->image) & 15)) img_dev = d->image;
     } else if (pinned_image && !(((size_t)d->image) & 15)) {
         void* p_ = nullptr;
         if (hipHostGetDevicePointer(&p_, (void*)d->image, 0) == hipSuccess) img_dev = p_;
         else (void)hipGetLastError();
     }
-    if (!pinned_image && !device_image) {
+    if (!cur && !pinned_image && !device_image) {
         if (d->stride == d->width) memcpy(h + h_img, d->image, img);
         else for (int y = 0; y < d->height; ++y) memcpy(h + h_img + (size_t)y * d->width, d->image + (size_t)y * d->stride, (size_t)d->width);
         img_dev = hd + h_img;
@@ -2257,13 +2553,15 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
         memset(h + h_nt, 0, 4); memset(h + h_st, 0, sizeof(dsdtm_align_stats));
     };
     seed_run();
-    if (img_dev) TRACK_TRY(ingest_launch(img_dev, f->d, img, hd + h_run, g + g_run, run_bytes, stream));
+    if (int rc = frames_consume(ctx, plan.frames_seq, stream)) return fail(rc);      // pending frames among ref / kf / cur
+    if (cur) TRACK_TRY(ingest_launch(nullptr, nullptr, 0, hd + h_run, g + g_run, run_bytes, stream));   // Run's range only
+    else if (img_dev) TRACK_TRY(ingest_launch(img_dev, f->d, img, hd + h_run, g + g_run, run_bytes, stream));
     else {      // (a pinned image the device cannot address, or one that is not 16-byte aligned; a strided or odd device image: the copy engine)
         if (device_image) TRACK_TRY(hipMemcpy2DAsync(f->d, (size_t)d->width, d->image, (size_t)d->stride, (size_t)d->width, (size_t)d->height, hipMemcpyDeviceToDevice, stream));
         else TRACK_TRY(hipMemcpyAsync(f->d, pinned_image ? (const void*)d->image : (const void*)(h + h_img), img, hipMemcpyHostToDevice, stream));
         TRACK_TRY(ingest_launch(nullptr, nullptr, 0, hd + h_run, g + g_run, run_bytes, stream));
     }
-    if (int rc = dsdtm_pyrdown_batch_device(ctx, f->d, f->pitch, 1, pl.levels, pl.w, pl.h, st, pl.off, stream)) return fail(rc);
+    if (!cur) { if (int rc = dsdtm_pyrdown_batch_device(ctx, f->d, f->pitch, 1, pl.levels, pl.w, pl.h, st, pl.off, stream)) return fail(rc); }
 
     // 2. Run(cur, ref) on the device copy of its range
     // Run() (:34-38): too few features -> 0, the pose untouched. Decided on the host: no launch.
@@ -2367,6 +2665,7 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
         pa.force_variant = 3;                                      // one wave / four waves by the match count, chosen by the kernel
         TRACK_TRY(pose_opt_launch(pa, stream));
         TRACK_TRY(hipStreamSynchronize(stream));
+        frames_settle(ctx);
         if (!*h_flag) break;
         *h_flag = 0;
         if (!multi_cu || attempt == 1 || options().no_recover) {
@@ -2390,7 +2689,7 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
     res->n_in_grid = cnt[0];
     res->n_matches = res->lost ? 0 : cnt[1];
     res->replay_full_scan = cnt[2] == 1 ? 1 : 0;
-    if (cnt[2] == 2 && !res->lost) { set_err(ctx, "track: the replay of the cell walk did not settle"); dsdtm_frame_destroy(ctx, f); res->frame = nullptr; return DSDTM_ERR_HIP; }
+    if (cnt[2] == 2 && !res->lost) { set_err(ctx, "track: the replay of the cell walk did not settle"); if (!cur) dsdtm_frame_destroy(ctx, f); res->frame = nullptr; return DSDTM_ERR_HIP; }
     if (res->lost) {
         memcpy(res->T_opt, res->T_run, 96);
     } else {
@@ -2400,6 +2699,23 @@ extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const 
         if (res->summary.n_residual_blocks > 0) memcpy(residual_norm, h + h_rn, (size_t)res->summary.n_residual_blocks * 8);
     }
     return DSDTM_OK;
+}
+
+extern "C" int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, dsdtm_track_result* res,
+                                 dsdtm_track_match* matches, double* residual_norm) {
+    if (!ctx) return DSDTM_ERR_INVALID;
+    if (!cam || !d || !res || !matches || !residual_norm) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
+    return track_frame_impl(ctx, cam, d, nullptr, res, matches, residual_norm);
+}
+
+extern "C" int dsdtm_track_frame_on(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, dsdtm_frame* cur,
+                                    dsdtm_track_result* res, dsdtm_track_match* matches, double* residual_norm) {
+    if (!ctx) return DSDTM_ERR_INVALID;
+    if (!cam || !d || !cur || !res || !matches || !residual_norm) {
+        set_err(ctx, "track_frame_on: NULL argument (%s)", !cam ? "cam" : !d ? "desc" : !cur ? "cur" : !res ? "result" : !matches ? "matches" : "residual_norm");
+        return DSDTM_ERR_INVALID;
+    }
+    return track_frame_impl(ctx, cam, d, cur, res, matches, residual_norm);
 }
 
 // ---- n independent tracked frames in ONE submission ------------------------------------------------
@@ -2559,7 +2875,10 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
 
     // ---- the slab ----
     const size_t slab_bytes = pitch * NF;
-    uint8_t* slab = pool_take(ctx, slab_bytes);
+    unsigned long long frames_seq = 0;          // the latest prefetch number among the pooled slab, the reference frames and the keyframes
+    uint8_t* slab = pool_take(ctx, slab_bytes, &frames_seq);
+    const unsigned long long slab_seq = frames_seq;   // (a pooled buffer whose prefetch may still be writing it: it goes back with this number)
+    for (int f = 0; f < n; ++f) if (plans[(size_t)f].frames_seq > frames_seq) frames_seq = plans[(size_t)f].frames_seq;
     if (!slab && (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&slab, slab_bytes) != hipSuccess)) {
         (void)hipGetLastError();
         set_err(ctx, "hipMalloc of a %zu-byte slab of %d frames failed", slab_bytes, n);
@@ -2568,7 +2887,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
     auto fail = [&](int rc) {
         if (ctx->copy_stream[0]) (void)hipStreamSynchronize(ctx->copy_stream[0]);
         (void)hipStreamSynchronize(stream);
-        if (!pool_give(ctx, ctx, ctx->device, slab, slab_bytes)) (void)hipFree(slab);
+        if (!pool_give(ctx, ctx, ctx->device, slab, slab_bytes, slab_seq)) (void)hipFree(slab);
         return rc;
     };
 #define TRACKS_TRY(call)                                                                                       \
@@ -2577,6 +2896,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
     } while (0)
 
+    if (int rc = frames_consume(ctx, frames_seq, stream)) return fail(rc);
     // ---- 1. Run's range: features, poses seeded (src/Tracking.cpp:201), counts and statistics cleared ----
     for (int s = 0; s < n; ++s) {
         const dsdtm_track_desc* d = &descs[order[(size_t)s]];
@@ -2736,6 +3056,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
     TRACKS_TRY(hipMemcpyAsync(h + h_T, g + g_run + (h_T - h_run), run_out_bytes, hipMemcpyDeviceToHost, stream));
     if (in_grid) TRACKS_TRY(hipMemcpyAsync(h + h_grid, g + g_grid, C, hipMemcpyDeviceToHost, stream));
     TRACKS_TRY(hipStreamSynchronize(stream));
+    frames_settle(ctx);
     if (*h_flag) {
         *h_flag = 0;
         for (int i = 0; i < dsdtm_ctx::MAX_STREAMS; ++i)

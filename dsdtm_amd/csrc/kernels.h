@@ -260,6 +260,22 @@ size_t local_ba_workspace_bytes(int n_pts, int n_obs);
 hipError_t local_ba_check_launch(const LocalBaArgs& args, hipStream_t stream);   // the device-side checks (reads only)
 hipError_t local_ba_launch(const LocalBaArgs& args, hipStream_t stream);         // the solve, on checked problems
 
+// RGB-D frames (rgbd.hip). Depth map of a frame: u16 rows `src_stride` elements apart (host-mapped pinned or device memory)
+// -> a packed w x h float plane, depth * inv_scale.
+hipError_t depth_ingest_launch(const uint16_t* src, int src_stride, float* dst, int w, int h, float inv_scale, int num_cus,
+                               hipStream_t stream);
+// Frame::Get_FeatureDetph + Frame::UnProject for n pixels on a frame's float depth plane (one thread per pixel).
+struct LiftArgs {
+    const float* depth; int w, h;   // the packed plane
+    float fx, fy, cx, cy;
+    double T[12];                   // mT_c2w: [R|t] row-major, world -> camera
+    const float* px_xy;             // n x 2
+    float* depth_out;               // n
+    double* p_world;                // n x 3
+    int n;
+};
+hipError_t lift_launch(const LiftArgs& args, hipStream_t stream);
+
 #ifdef DSDTM_DIAG
 // device self-test of the FP64 building blocks (wave reduction, LDLT, SE3); see selftest.hip (diagnostic build only)
 hipError_t selftest_launch(const double* in, double* out, int n_cases, hipStream_t stream);

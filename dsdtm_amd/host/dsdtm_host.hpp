@@ -107,6 +107,44 @@ struct Frame {                                    // include/Frame.h (what the p
         if (dsdtm_frame_create_from_image(detail::ctx(), l0.data.data(), l0.cols, l0.rows, l0.step, levels, &mDev) != DSDTM_OK)
             throw std::runtime_error(std::string("dsdtm_frame_create_from_image: ") + dsdtm_last_error(detail::ctx()));
     }
+    // The frame's way into the device AHEAD of its tracking (dsdtm_frame_prefetch): level 0, the pyramid and — with a depth
+    // image, the cv::Mat CV_16U that Tracking::Track_RGBDCam receives (src/Tracking.cpp:45-57) — the depth map in metres are
+    // enqueued on the library's prefetch stream and the call returns at once. depth: rows of `cols` uint16, depth_step
+    // ELEMENTS apart, or null. Pageable images are staged before the call returns; pinned ones are read in place (keep them
+    // unchanged until the frame has been used by a call, or dsdtm_frame_wait).
+    void PrefetchOnDevice(int levels, const uint16_t* depth = nullptr, int depth_step = 0, float depth_scale = 5000.0f) {
+        if (mDev || mvImg_Pyr.empty()) return;
+        const Image8& l0 = mvImg_Pyr[0];
+        dsdtm_frame_image im{};
+        im.gray = l0.data.data(); im.width = l0.cols; im.height = l0.rows; im.stride = l0.step; im.levels = levels;
+        im.depth = depth; im.depth_stride = depth ? depth_step : 0; im.depth_scale = depth_scale;
+        if (dsdtm_frame_prefetch(detail::ctx(), &im, &mDev) != DSDTM_OK)
+            throw std::runtime_error(std::string("dsdtm_frame_prefetch: ") + dsdtm_last_error(detail::ctx()));
+    }
+    // Frame::Get_FeatureDetph(cv::Point2f) (src/Frame.cpp:201-224) and Frame::UnProject (:152-157) on the resident depth map:
+    // dsdtm_frame_lift for one pixel (CraeteKeyframe's loop, src/Tracking.cpp:436-440, hands all its pixels over in one call —
+    // INTEGRATION.md §5e). -1: no depth at the pixel or its four neighbours. The two single-pixel forms exist for source
+    // compatibility only: each is a synchronous round trip to the device — loops use Lift.
+    float Get_FeatureDetph(float px_x, float px_y) const {
+        float d = -1.0f; double p[3];
+        Lift(&px_x, &px_y, 1, &d, p);
+        return d;
+    }
+    std::array<double, 3> UnProject(float px_x, float px_y, float* depth = nullptr) const {
+        float d = -1.0f; double p[3];
+        Lift(&px_x, &px_y, 1, &d, p);
+        if (depth) *depth = d;
+        return {{p[0], p[1], p[2]}};
+    }
+    void Lift(const float* px_x, const float* px_y, int n, float* depth_out, double* p_world_out) const {
+        if (!mDev) throw std::runtime_error("Frame::Lift: the frame is not resident on the device");
+        std::vector<float> px(2 * (size_t)n);
+        for (int i = 0; i < n; ++i) { px[2 * (size_t)i] = px_x[i]; px[2 * (size_t)i + 1] = px_y[i]; }
+        const Camera& c = *mCamera;
+        const dsdtm_camera cam{c.mfx, c.mfy, c.mcx, c.mcy, c.mf, c.mwidth, c.mheight};
+        if (dsdtm_frame_lift(detail::ctx(), mDev, &cam, mT_c2w.m.data(), px.data(), n, depth_out, p_world_out) != DSDTM_OK)
+            throw std::runtime_error(std::string("dsdtm_frame_lift: ") + dsdtm_last_error(detail::ctx()));
+    }
     Frame() = default;
     Frame(const Frame&) = delete;
     Frame& operator=(const Frame&) = delete;
@@ -574,8 +612,10 @@ public:
 
     // level0: the new image. `last`, the keyframes: frames whose pyramids are resident (ComputeImagePyramidOnDevice).
     // local_points: the order UpdateLocalMap would hand them to ReprojectPoint (:283-299). img_mask: Frame::mImgMask or null.
+    // prefetched: a frame that was sent ahead (Frame::PrefetchOnDevice, called for frame k + 1 BEFORE TrackFrame of frame k):
+    // tracking then starts at Run on it (dsdtm_track_frame_on) and it is the frame returned; null: the frame is made from level0.
     FramePtr TrackFrame(const Image8& level0, const FramePtr& last, const std::vector<Frame*>& keyframes,
-                        const std::vector<MapPoint*>& local_points, Image8* img_mask, Result* out) {
+                        const std::vector<MapPoint*>& local_points, Image8* img_mask, Result* out, FramePtr prefetched = nullptr) {
         const int levels = mMaxLevel;
         const std::vector<Feature>& rf = last->mvFeatures;
         const size_t n = rf.size(), M = local_points.size();
@@ -625,11 +665,15 @@ public:
         dsdtm_track_result r;
         std::vector<dsdtm_track_match> ms(200);
         std::vector<double> rn(200);
-        if (dsdtm_track_frame(detail::ctx(), &cam, &d, &r, ms.data(), rn.data()) != DSDTM_OK)
+        if (prefetched && prefetched->mDev) {
+            d.image = nullptr;
+            if (dsdtm_track_frame_on(detail::ctx(), &cam, &d, prefetched->mDev, &r, ms.data(), rn.data()) != DSDTM_OK)
+                throw std::runtime_error(std::string("dsdtm_track_frame_on: ") + dsdtm_last_error(detail::ctx()));
+        } else if (dsdtm_track_frame(detail::ctx(), &cam, &d, &r, ms.data(), rn.data()) != DSDTM_OK)
             throw std::runtime_error(std::string("dsdtm_track_frame: ") + dsdtm_last_error(detail::ctx()));
-        FramePtr cur = std::make_shared<Frame>();
+        FramePtr cur = (prefetched && prefetched->mDev) ? prefetched : std::make_shared<Frame>();
         cur->mCamera = mCam;
-        cur->mvImg_Pyr.push_back(level0);                                  // (level 0 on the host; the pyramid lives on the device)
+        if (cur->mvImg_Pyr.empty()) cur->mvImg_Pyr.push_back(level0);      // (level 0 on the host; the pyramid lives on the device)
         cur->mDev = r.frame;
         SE3 T; std::copy(r.T_run, r.T_run + 12, T.m.begin());
         cur->Set_Pose(T);                                                  // src/Sprase_ImageAlign.cpp:57

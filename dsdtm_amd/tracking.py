@@ -50,19 +50,28 @@ def flatten_local_map(keyframes, map_points):
 class TrackCall:
     """One prepared dsdtm_track_frame call: the descriptor and every array it points at are built once (`__init__`), `run()`
     is the library call alone — what a C++ Tracking pays per frame (bench_tracking.py times it; a frame's release is the
-    caller's: result["frame"].close())."""
+    caller's: result["frame"].close()). With `cur_frame` (a capi.DeviceFrame from DeviceFrame.prefetch or .from_image) the call is
+    dsdtm_track_frame_on: the new frame is already on the device, or on its way there, `image` is not read (it may be None) and
+    result["frame"] is cur_frame."""
 
     def __init__(self, ctx: capi.Context, cam, image, levels, last: Frame, T_seed, align, min_tracked, keyframes, map_points,
-                 mask=None, cell_size=None, max_pyr_levels=None, max_matches=200, align2d_iters=10, po_iterations=100, flat=None):
+                 mask=None, cell_size=None, max_pyr_levels=None, max_matches=200, align2d_iters=10, po_iterations=100, flat=None,
+                 cur_frame=None):
         self.ctx = ctx
+        self.cur_frame = cur_frame
+        if cur_frame is not None:
+            image = np.zeros((0, 0), np.uint8)                 # (never read: the descriptor's image stays NULL)
         image = np.asarray(image)
-        if image.dtype != np.uint8 or image.ndim != 2 or image.strides[1] != 1 or image.strides[0] < image.shape[1]:
+        if cur_frame is None and (image.dtype != np.uint8 or image.ndim != 2 or image.strides[1] != 1 or image.strides[0] < image.shape[1]):
             image = np.ascontiguousarray(image, np.uint8)      # (a row-strided uint8 view goes down as it is: d.stride)
         cell_size = int(Config.Get("Camera.CellSize") if cell_size is None else cell_size)
         max_pyr_levels = int(Config.Get("Camera.MaxPyraLevels") if max_pyr_levels is None else max_pyr_levels)
         fm = flat if flat is not None else flatten_local_map(keyframes, map_points)
         d = capi.TrackDesc()
-        d.image, d.width, d.height, d.stride, d.levels = image.ctypes.data, image.shape[1], image.shape[0], image.strides[0], int(levels)
+        if cur_frame is None:
+            d.image, d.width, d.height, d.stride, d.levels = image.ctypes.data, image.shape[1], image.shape[0], image.strides[0], int(levels)
+        else:
+            d.image, d.width, d.height, d.stride, d.levels = None, cam.width, cam.height, cam.width, int(levels)
         dref = capi.device_frame_of(ctx, last)
         d.ref = dref.handle
         px = np.ascontiguousarray(last.px, np.float32)
@@ -95,6 +104,9 @@ class TrackCall:
 
     def run_raw(self) -> int:
         """The library call alone; returns its status (the new frame's handle is in self.res.frame)."""
+        if self.cur_frame is not None:
+            return self.ctx.lib.dsdtm_track_frame_on(self.ctx.handle, C.byref(self.cs), C.byref(self.desc), self.cur_frame.handle,
+                                                     C.byref(self.res), self.matches.ctypes.data, self.rn.ctypes.data)
         return self.ctx.lib.dsdtm_track_frame(self.ctx.handle, C.byref(self.cs), C.byref(self.desc), C.byref(self.res),
                                               self.matches.ctypes.data, self.rn.ctypes.data)
 
@@ -102,7 +114,8 @@ class TrackCall:
         self.ctx.check(self.run_raw())
         res = self.res
         sm = res.summary.as_dict()
-        return dict(frame=capi.DeviceFrame(self.ctx, C.c_void_p(res.frame)), T_run=np.array(list(res.T_run)).reshape(3, 4),
+        frame = self.cur_frame if self.cur_frame is not None else capi.DeviceFrame(self.ctx, C.c_void_p(res.frame))
+        return dict(frame=frame, T_run=np.array(list(res.T_run)).reshape(3, 4),
                     n_tracked=int(res.n_tracked), lost=bool(res.lost), stats=res.stats.as_dict(), n_in_grid=int(res.n_in_grid),
                     replay_full_scan=bool(res.replay_full_scan), matches=self.matches[:res.n_matches].copy(),
                     T_opt=np.array(list(res.T_opt)).reshape(3, 4), summary=sm, residual_norm=self.rn[:sm["n_residual_blocks"]].copy())
@@ -203,12 +216,32 @@ class Tracker:
         self.max_iters = int(Config.Get("Optimization.MaxIter") if max_iters is None else max_iters)
         self.min_tracked = int(min_tracked)
         self.last_result = None
+        self._prefetched = []          # [(image, capi.DeviceFrame)] in the order prefetch() was called
+
+    def prefetch(self, image, depth=None, depth_scale: float = 5000.0):
+        """Optional: sends a frame to the device ahead of its TrackFrame (dsdtm_frame_prefetch; returns at once). The capture
+        loop calls it for frame k + 1 BEFORE TrackFrame of frame k, so that the upload and the pyramid of k + 1 run beside the
+        tracking of k; TrackFrame(image, ...) with the same image object then starts at Run on that frame. With `depth` (uint16)
+        the frame also carries the depth map, for DeviceFrame.lift. Returns the capi.DeviceFrame. At most two frames are kept
+        (k and k + 1): a third prefetch releases the oldest one that TrackFrame never asked for."""
+        df = capi.DeviceFrame.prefetch(self.ctx, image, self.levels, depth, depth_scale)
+        self._prefetched.append((image, df))
+        while len(self._prefetched) > 2:
+            self._prefetched.pop(0)[1].close()
+        return df
 
     def TrackFrame(self, image, last: Frame, keyframes, map_points, img_mask=None):
         """Returns (cur Frame, n_tracked, matches as [(cell, MapPoint, px float32[2], level)])."""
+        cur_frame = None
+        at = next((i for i, (im, _) in enumerate(self._prefetched) if im is image), None)
+        if at is not None:                     # frames prefetched before it were skipped by the caller: released
+            for _, stale in self._prefetched[:at]:
+                stale.close()
+            cur_frame = self._prefetched[at][1]
+            del self._prefetched[:at + 1]
         r = track_frame(self.ctx, self.cam, image, self.levels, last, last.Get_Pose(),
                         (self.levels, self.min_level, self.max_iters, int(Config.Get("Camera.Min_fts"))), self.min_tracked,
-                        keyframes, map_points, mask=img_mask)
+                        keyframes, map_points, mask=img_mask, cur_frame=cur_frame)
         self.last_result = r
         return apply_tracked_frame(self.cam, image, r, map_points, img_mask)
 

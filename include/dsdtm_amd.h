@@ -425,6 +425,50 @@ typedef struct dsdtm_track_result {
 int dsdtm_track_frame(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* desc,
                       dsdtm_track_result* result, dsdtm_track_match* matches, double* residual_norm);
 
+/* ---- RGB-D frames that enter the device ahead of time (src/Frame.cpp:35-41, src/Tracking.cpp:56-57) -------------------
+ * Neither the upload of a new image nor its pyramid reads a pose, so a tracker can send frame k + 1 while frame k is being
+ * tracked: dsdtm_frame_prefetch enqueues level 0, the pyramid and (if given) the depth map on a stream of its own and
+ * returns at once; dsdtm_track_frame_on is dsdtm_track_frame starting at Run on such a frame. The depth map travels with the
+ * frame, and Frame::Get_FeatureDetph + Frame::UnProject (src/Frame.cpp:152-157, 176-199, 201-224: the lift that turns a
+ * keyframe's new features into map points, src/Tracking.cpp:436-440, :158-163) become a query on the resident frame.
+ *
+ * gray ... levels : the image, as dsdtm_track_desc.image (pageable or pinned host memory, or the context's device).
+ * depth           : height rows of `width` u16, depth_stride ELEMENTS apart (>= width), host or device memory; NULL = no
+ *                   depth map. The frame keeps depth * (float)(1.0f / depth_scale) as floats:
+ *                   tDImg.convertTo(CV_32F, 1.0f / mDepthScale) (src/Tracking.cpp:56).
+ * depth_scale     : Camera.depth_scale (src/Tracking.cpp:23); > 0 when depth != NULL.
+ *
+ * The caller's buffers. An image (gray or depth) in pageable host memory, and a pinned gray image with padded rows, is
+ * STAGED — copied into pinned memory of the context before the call returns: the caller may change it as soon as the call has
+ * returned. Every other image (pinned host memory, device memory) is READ IN PLACE by the prefetch stream: the caller may
+ * change it only after dsdtm_frame_wait on the frame, or after the return of the first synchronous entry that consumed the
+ * frame (any entry that takes it as an argument).
+ * Pending frames are ordinary frames: every entry that takes a dsdtm_frame orders its own stream behind the frame's event
+ * (no host wait); dsdtm_frame_destroy on a pending frame is legal. Not inside a stream capture (DSDTM_ERR_INVALID). */
+typedef struct dsdtm_frame_image {          /* what src/Frame.cpp:35-41 is constructed from */
+    const uint8_t*  gray;  int32_t width, height, stride, levels;      /* as dsdtm_track_desc.image */
+    const uint16_t* depth; int32_t depth_stride;  /* elements per row; depth == NULL: no depth map */
+    float depth_scale;                            /* Camera.depth_scale (src/Tracking.cpp:23) */
+} dsdtm_frame_image;
+int dsdtm_frame_prefetch(dsdtm_ctx* ctx, const dsdtm_frame_image* image, dsdtm_frame** out);   /* returns at once */
+int dsdtm_frame_wait(dsdtm_ctx* ctx, const dsdtm_frame* frame);                                /* the host waits until the frame is resident */
+/* dsdtm_track_frame on a frame that is already on the device (from dsdtm_frame_prefetch, pending or not, or from
+ * dsdtm_frame_create_from_image): desc->image must be NULL and desc->width / height / levels must be the frame's. Every field of
+ * the result, the matches and the residual norms are those of dsdtm_track_frame on the same image, bit for bit;
+ * result->frame == cur (still the caller's to destroy, also when the call fails). */
+int dsdtm_track_frame_on(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* desc, dsdtm_frame* cur,
+                         dsdtm_track_result* result, dsdtm_track_match* matches, double* residual_norm);
+/* Frame::Get_FeatureDetph(cv::Point2f) followed by Frame::UnProject for n pixels of a frame with a depth map (synchronous;
+ * n <= DSDTM_LIFT_MAX). Per pixel: cvRound of the two float members; the depth at the rounded pixel, else the first non-zero
+ * of its neighbours in the order (-1,0), (0,-1), (1,0), (0,1), else -1 (a rounded pixel or neighbour outside the image has
+ * no depth: the reference indexes the cv::Mat unchecked there; so has a NaN or infinite coordinate). Then Camera::Pixel2Camera(Point2f, d) in FLOAT
+ * (src/Camera.cpp:173-178: d*(x-cx)/fx, d*(y-cy)/fy, d), widened to double, and mT_c2w.inverse() * p as Sophus evaluates it,
+ * R^T p + (-(R^T t)), in double. depth_out[i] == -1 leaves p_world_out[3i .. 3i+2] at 0.
+ * T_c2w : 12, the frame's pose [R|t] (world -> camera); px_xy : n x 2 float; depth_out : n float; p_world_out : n x 3 double. */
+#define DSDTM_LIFT_MAX 16384
+int dsdtm_frame_lift(dsdtm_ctx* ctx, const dsdtm_frame* frame, const dsdtm_camera* cam, const double* T_c2w,
+                     const float* px_xy, int n, float* depth_out, double* p_world_out);
+
 /* ---- n independent tracked frames in ONE submission ------------------------------------------------------------------
  * dsdtm_track_frame for the frames of n independent trackers (a multi-camera rig, offline re-tracking of a dataset, many
  * robots on one server): one call, one submission, one wait. Per frame the results are those of dsdtm_track_frame on the same
