@@ -402,6 +402,21 @@ class debug_options:
         return False
 
 
+def track_frames(ctx, cam, n, descs, results, matches, residual_norm, in_grid, frames=None) -> int:
+    """dsdtm_track_frames; returns its status. `descs` / `results`: ctypes arrays of n TrackDesc / TrackResult; `matches`,
+    `residual_norm`, `in_grid`: addresses (in_grid may be None). frames=[DeviceFrame, ...] (n of them) is the resident mode: the
+    frames are already on the device, or on their way there (DeviceFrame.prefetch) — every descriptor's image is set to NULL and
+    results[f].frame names frame f on entry; it is the same handle on return, and the frame stays the caller's."""
+    if frames is not None:
+        if len(frames) != n:
+            raise ValueError(f"{len(frames)} resident frames for {n} descriptors")
+        for f, df in enumerate(frames):
+            descs[f].image = None
+            results[f].frame = df.handle.value if isinstance(df.handle, C.c_void_p) else df.handle
+    return ctx.lib.dsdtm_track_frames(ctx.handle, C.byref(cam) if isinstance(cam, Camera) else C.byref(camera_struct(cam)), n, descs,
+                                      results, matches, residual_norm, in_grid)
+
+
 def device_frame_of(ctx, frame):
     """The frame's pyramid on the device (uploaded on first use, cached on the Frame object)."""
     df = getattr(frame, "_device_frame", None)

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <new>
@@ -102,10 +103,12 @@ struct dsdtm_ctx {
     // dsdtm_frame_prefetch: a stream of its own, created on first use. Prefetched frames are numbered in the order they were
     // enqueued on it; the stream runs in order, so "frame n is resident" implies every earlier one is. Event n % PREFETCH_EVENTS
     // is recorded behind frame n (a wait on an event that a later frame has re-recorded waits a little longer, never too
-    // short). prefetch_settled: the highest number the HOST knows to be resident — frames up to it cost nothing more;
+    // short). The ring is as long as two full batches of dsdtm_track_frames: with step k + 1 of 1024 trackers prefetched before
+    // step k is tracked, the event behind step k's last frame is still its own, and the call does not wait for step k + 1.
+    // An event is created when its place in the ring is first used. prefetch_settled: the highest number the HOST knows to be resident — frames up to it cost nothing more;
     // prefetch_waiting: the highest number the context's stream has been told to wait for (hipStreamWaitEvent) — it becomes
     // prefetch_settled at the next host synchronisation of that stream.
-    static constexpr int PREFETCH_EVENTS = 4;
+    static constexpr int PREFETCH_EVENTS = 4096;
     hipStream_t prefetch_stream = nullptr;
     hipEvent_t prefetch_event[PREFETCH_EVENTS] = {};
     unsigned long long prefetch_seq = 0, prefetch_settled = 0, prefetch_waiting = 0;
@@ -403,6 +406,7 @@ struct LaunchMode {
     bool single = false;        // synchronous single-pair entry: its own timeout word, settled by the caller itself
     int variant = -1;           // >= 0: this register variant, whatever max_features (dsdtm_track_frames: max_features is a stride)
     const uint8_t* const* ref_ptrs = nullptr;   // device table of the pairs' reference pyramids (dsdtm_track_frames)
+    const uint8_t* const* cur_ptrs = nullptr;   // ... and of their current pyramids (resident frames; with ref_ptrs only)
 };
 static int launch_batch(dsdtm_ctx* ctx, const dsdtm_batch_desc* b, const dsdtm_camera* cam, const dsdtm_align_params* prm,
                         void* hip_stream, const LaunchMode& mode, bool* multi_cu_used);
@@ -580,6 +584,7 @@ static int launch_batch(dsdtm_ctx* ctx, const dsdtm_batch_desc* b, const dsdtm_c
     const SAVariant v = mode.variant >= 0 ? (SAVariant)mode.variant : sparse_align_pick_variant(b->max_features);
     const size_t ws = mode.variant >= 0 ? 0 : sparse_align_workspace_bytes(b->n_pairs, b->max_features);
     a.ref_ptrs = mode.ref_ptrs;
+    a.cur_ptrs = mode.ref_ptrs ? mode.cur_ptrs : nullptr;
     const bool duo = !team_k && multi_cu && sparse_align_uses_duo(b->max_features, ws != 0);
     int slot = -1;
     if ((team_k || duo) && !mode.single) {
@@ -1402,7 +1407,10 @@ extern "C" int dsdtm_frame_prefetch(dsdtm_ctx* ctx, const dsdtm_frame_image* im,
     const int gray_mem = image_memory(ctx, im->gray), depth_mem = im->depth ? image_memory(ctx, im->depth) : 0;
     if (gray_mem < 0 || depth_mem < 0) { set_err(ctx, "prefetch: image->%s lives on another device than the context's (%d)", gray_mem < 0 ? "gray" : "depth", ctx->device); return DSDTM_ERR_INVALID; }
     if (!ctx->prefetch_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->prefetch_stream, hipStreamNonBlocking));
-    for (auto& e : ctx->prefetch_event) if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    {
+        hipEvent_t& e = ctx->prefetch_event[(ctx->prefetch_seq + 1) % dsdtm_ctx::PREFETCH_EVENTS];    // this frame's
+        if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
     hipStream_t ps = ctx->prefetch_stream;
 
     PackedPyr pl;
@@ -2726,6 +2734,12 @@ extern "C" int dsdtm_track_frame_on(dsdtm_ctx* ctx, const dsdtm_camera* cam, con
 // one workgroup per frame; the pose refinement, one instantiation per frame by its match count. The host waits once.
 // Inside the call frames sit in SLOT order — sorted by register band, so that each band's pairs are contiguous in the Run
 // arrays and in the slab — and are handed back in the caller's order.
+// RESIDENT MODE (descs[f].image == NULL for every f): the new frames are already on the device, or on their way there —
+// results[f].frame names frame f on entry (dsdtm_frame_prefetch, pending or not; dsdtm_frame_create_from_image; a member of an
+// earlier call's slab). No slab, no ingest of images, no pyramid kernel: the chain starts at Run, behind a device-side wait for
+// the latest prefetch among all frames named. The frames are separate allocations in the caller's order, so Run and the
+// FindMatchDirect kernel find slot s's current pyramid through a table (cur_ptrs, in Run's range beside ref_ptrs). The frames
+// stay the caller's: results[f].frame is the same pointer on return, on success and on every failure.
 static int track_band(const dsdtm_track_desc* d) {
     const bool run = d->n_ref_features >= d->align.min_fts && d->align.max_level - 1 >= d->align.min_level && d->n_ref_features > 0;
     if (!run) return 7;                                            // no Run launch (the Min_fts rule, as the single call)
@@ -2747,7 +2761,23 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
     if (n_frames == 0) return DSDTM_OK;
     if (!cam || !descs || !results || !matches || !residual_norm) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
     const int n = n_frames;
-    for (int f = 0; f < n; ++f) memset(&results[f], 0, sizeof results[f]);
+    const bool resident = descs[0].image == nullptr;               // all or none: frame 0 decides, every other frame must agree
+    // (checked before `results` is touched: in a mixture some results[f].frame are the caller's frames, and stay so)
+    for (int f = 0; f < n; ++f)
+        if ((descs[f].image == nullptr) != resident) {
+            set_err(ctx, "track_frames: frame %d: image is %s, frame 0's is %s (a call runs on resident frames — image NULL, results[f].frame set — for all of its frames or for none)",
+                    f, descs[f].image ? "set" : "NULL", resident ? "NULL" : "set");
+            return DSDTM_ERR_INVALID;
+        }
+    std::vector<dsdtm_frame*> cur;                                 // resident mode: the frames, in the caller's order
+    if (resident) {
+        try { cur.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+        for (int f = 0; f < n; ++f) cur[(size_t)f] = results[f].frame;
+    }
+    for (int f = 0; f < n; ++f) {
+        memset(&results[f], 0, sizeof results[f]);
+        if (resident) results[f].frame = cur[(size_t)f];           // in/out: the caller's before, during and after the call
+    }
     // ---- every frame is checked before anything is allocated or enqueued ----
     std::vector<TrackPlan> plans;
     try { plans.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
@@ -2767,7 +2797,19 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         else if (d->align2d_iters != d0.align2d_iters) field = "align2d_iters";
         else if (d->pose_opt.max_iterations != d0.pose_opt.max_iterations) field = "pose_opt";
         if (field) { set_err(ctx, "track_frames: frame %d: %s differs from frame 0 (shared across the batch)", f, field); return DSDTM_ERR_INVALID; }
-        if (int rc = track_check_desc(ctx, cam, d, &plans[(size_t)f])) {
+        if (resident) {
+            const dsdtm_frame* c = cur[(size_t)f];
+            if (!c) { set_err(ctx, "track_frames: frame %d: results[%d].frame is NULL (image is NULL: the frame must already be on the device)", f, f); return DSDTM_ERR_INVALID; }
+            if (c->owner != ctx || c->device != ctx->device) { set_err(ctx, "track_frames: frame %d: results[%d].frame belongs to another context", f, f); return DSDTM_ERR_INVALID; }
+            const char* geom = c->pl.w[0] != d->width ? "width" : c->pl.h[0] != d->height ? "height" : c->pl.levels != d->levels ? "levels" : nullptr;
+            if (geom) {
+                set_err(ctx, "track_frames: frame %d: desc %s (%dx%d, %d levels) is not results[%d].frame's (%dx%d, %d levels)", f, geom, d->width,
+                        d->height, d->levels, f, c->pl.w[0], c->pl.h[0], c->pl.levels);
+                return DSDTM_ERR_INVALID;
+            }
+            if (c == d->ref) { set_err(ctx, "track_frames: frame %d: ref is results[%d].frame itself", f, f); return DSDTM_ERR_INVALID; }
+        }
+        if (int rc = track_check_desc(ctx, cam, d, &plans[(size_t)f], resident)) {
             char msg[sizeof ctx->err];
             snprintf(msg, sizeof msg, "%s", ctx->err);
             set_err(ctx, "track_frames: frame %d: %s", f, msg);
@@ -2775,6 +2817,26 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         }
         if (d->n_ref_features > 704) { set_err(ctx, "track_frames: frame %d: %d reference features (at most 704)", f, d->n_ref_features); return DSDTM_ERR_INVALID; }
         if (d->ref->pitch != align_up(plans[(size_t)f].pl.bytes, 256)) { set_err(ctx, "track_frames: frame %d: pyramid pitches differ", f); return DSDTM_ERR_INVALID; }
+        if (resident) {
+            const dsdtm_frame* c = cur[(size_t)f];
+            const PackedPyr& q = plans[(size_t)f].pl;
+            // (a frame from dsdtm_frame_create with levels or a pitch of its own)
+            if (memcmp(c->pl.w, q.w, sizeof(int) * q.levels) || memcmp(c->pl.h, q.h, sizeof(int) * q.levels) || memcmp(c->pl.off, q.off, sizeof(q.off[0]) * q.levels) ||
+                c->pitch != d->ref->pitch) {
+                set_err(ctx, "track_frames: frame %d: levels of results[%d].frame are not those of a %dx%d image with %d levels", f, f, d->width, d->height, d->levels);
+                return DSDTM_ERR_INVALID;
+            }
+            if (c->seq > plans[(size_t)f].frames_seq) plans[(size_t)f].frames_seq = c->seq;
+        }
+    }
+    if (resident) {                                                // the same frame twice: named by its later place in the call
+        std::vector<std::pair<const dsdtm_frame*, int>> by_ptr;
+        try { for (int f = 0; f < n; ++f) by_ptr.emplace_back(cur[(size_t)f], f); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+        std::sort(by_ptr.begin(), by_ptr.end());
+        int dup = -1, first = -1;
+        for (size_t i = 1; i < by_ptr.size(); ++i)
+            if (by_ptr[i].first == by_ptr[i - 1].first && (dup < 0 || by_ptr[i].second < dup)) { dup = by_ptr[i].second; first = by_ptr[i - 1].second; }
+        if (dup >= 0) { set_err(ctx, "track_frames: frame %d: results[%d].frame is also frame %d's (a frame at most once per call)", dup, dup, first); return DSDTM_ERR_INVALID; }
     }
     const TrackPlan& P = plans[0];
     const PackedPyr& pl = P.pl;
@@ -2816,7 +2878,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
     // Run's range (slot order, features at stride MF): inputs, then the poses / counts / statistics Run writes
     const size_t h_run = o;
     const size_t h_px = take(NF * MF * 8), h_bear = take(NF * MF * 24), h_pw = take(NF * MF * 24), h_ini = take(NF * MF),
-                 h_nf = take(NF * 4), h_tr = take(NF * 96), h_rp = take(NF * sizeof(void*));
+                 h_nf = take(NF * 4), h_tr = take(NF * 96), h_rp = take(NF * sizeof(void*)), h_cp = take(resident ? NF * sizeof(void*) : 0);
     const size_t h_T = take(NF * 96), h_nt = take(NF * 4), h_st = take(NF * sizeof(dsdtm_align_stats));
     const size_t run_bytes = o - h_run, run_out_bytes = o - h_T;
     // the local maps and masks (slot order, columns padded): one range, copied up in one piece
@@ -2834,7 +2896,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
     std::vector<uint8_t> kind;   // 0: staged, 1: pinned (host-mapped), 2: device, 3: device through the copy engine, 4: pinned through the copy engine
     std::vector<const void*> src;
     try { kind.resize(NF); src.resize(NF); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
-    for (int f = 0; f < n; ++f) {
+    for (int f = 0; f < n && !resident; ++f) {
         const dsdtm_track_desc* d = &descs[f];
         bool pinned_image = false, device_image = false;
         hipPointerAttribute_t pa_;
@@ -2873,13 +2935,14 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
     uint8_t* const gr = g + g_run - h_run;      // device address of pinned offset X inside Run's range: gr + X
     uint8_t* const gm = g + g_map - h_map;      // ... inside the map range: gm + X
 
-    // ---- the slab ----
+    // ---- the slab (resident mode: none — the frames are where they are) ----
     const size_t slab_bytes = pitch * NF;
-    unsigned long long frames_seq = 0;          // the latest prefetch number among the pooled slab, the reference frames and the keyframes
-    uint8_t* slab = pool_take(ctx, slab_bytes, &frames_seq);
+    unsigned long long frames_seq = 0;          // the latest prefetch number among the pooled slab, the current (resident), reference and key frames
+    uint8_t* slab = resident ? nullptr : pool_take(ctx, slab_bytes, &frames_seq);
     const unsigned long long slab_seq = frames_seq;   // (a pooled buffer whose prefetch may still be writing it: it goes back with this number)
     for (int f = 0; f < n; ++f) if (plans[(size_t)f].frames_seq > frames_seq) frames_seq = plans[(size_t)f].frames_seq;
-    if (!slab && (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&slab, slab_bytes) != hipSuccess)) {
+    if (resident) HIP_TRY(ctx, hipSetDevice(ctx->device));
+    else if (!slab && (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&slab, slab_bytes) != hipSuccess)) {
         (void)hipGetLastError();
         set_err(ctx, "hipMalloc of a %zu-byte slab of %d frames failed", slab_bytes, n);
         return DSDTM_ERR_NOMEM;
@@ -2887,7 +2950,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
     auto fail = [&](int rc) {
         if (ctx->copy_stream[0]) (void)hipStreamSynchronize(ctx->copy_stream[0]);
         (void)hipStreamSynchronize(stream);
-        if (!pool_give(ctx, ctx, ctx->device, slab, slab_bytes, slab_seq)) (void)hipFree(slab);
+        if (slab && !pool_give(ctx, ctx, ctx->device, slab, slab_bytes, slab_seq)) (void)hipFree(slab);
         return rc;
     };
 #define TRACKS_TRY(call)                                                                                       \
@@ -2910,12 +2973,14 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         ((int32_t*)(h + h_nf))[s] = (int32_t)nf;
         memcpy(h + h_tr + S * 96, d->T_ref_w, 96);
         ((const uint8_t**)(h + h_rp))[s] = d->ref->d;
+        if (resident) ((const uint8_t**)(h + h_cp))[s] = cur[(size_t)order[S]]->d;
         memcpy(h + h_T + S * 96, d->T_seed, 96);
     }
     memset(h + h_nt, 0, NF * 4);
     memset(h + h_st, 0, NF * sizeof(dsdtm_align_stats));
     // ---- 2. the new frames: level 0 of each into its slot of the slab (the first ingest also moves Run's range), the pyramids ----
-    {
+    if (resident) TRACKS_TRY(ingest_launch(nullptr, nullptr, 0, hd + h_run, g + g_run, run_bytes, stream));   // Run's range only
+    else {
         size_t staged = 0;
         bool run_moved = false;
         for (int s = 0; s < n; ++s) {
@@ -2941,7 +3006,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
             run_moved = true;
         }
     }
-    if (int rc = dsdtm_pyrdown_batch_device(ctx, slab, pitch, n, pl.levels, pl.w, pl.h, P.st, pl.off, stream)) return fail(rc);
+    if (!resident) { if (int rc = dsdtm_pyrdown_batch_device(ctx, slab, pitch, n, pl.levels, pl.w, pl.h, P.st, pl.off, stream)) return fail(rc); }
 
     // ---- 3. Run: one launch per register band present, one-CU kernels, reference pyramids through the pointer table ----
     volatile unsigned* h_flag = ctx->h_flags + dsdtm_ctx::FLAG_SINGLE;
@@ -2955,8 +3020,8 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         bd.n_pairs = cnt; bd.max_features = (int)MF; bd.levels = pl.levels;
         for (int l = 0; l < pl.levels; ++l) { bd.width[l] = pl.w[l]; bd.height[l] = pl.h[l]; bd.stride[l] = pl.w[l]; bd.level_offset[l] = pl.off[l]; }
         bd.pyr_pitch = pitch;
-        bd.ref_pyr = slab + L * pitch;                            // (not read by the pointer-table kernel: a range of the right size)
-        bd.cur_pyr = slab + L * pitch;
+        bd.ref_pyr = resident ? cur[(size_t)order[L]]->d : slab + L * pitch;   // (not read by the pointer-table kernel: a range of the right size)
+        bd.cur_pyr = bd.ref_pyr;                                  // (resident: not read either — every pair goes through cur_ptrs)
         bd.px_xy = (const float*)(gr + h_px) + L * MF * 2; bd.bearing = (const double*)(gr + h_bear) + L * MF * 3;
         bd.p_world = (const double*)(gr + h_pw) + L * MF * 3; bd.initial = gr + h_ini + L * MF;
         bd.n_features = (const int32_t*)(gr + h_nf) + L;
@@ -2965,6 +3030,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         LaunchMode mode;
         mode.single = true; mode.one_cu = true; mode.variant = (int)kBandVariant[b];
         mode.ref_ptrs = (const uint8_t* const*)(gr + h_rp) + L;
+        if (resident) mode.cur_ptrs = (const uint8_t* const*)(gr + h_cp) + L;
         if (int rc = launch_batch(ctx, &bd, cam, &d0.align, stream, mode, nullptr)) return fail(rc);
     }
 
@@ -3029,6 +3095,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
     t.po_n = (int32_t*)(g + g_pon);
     t.n_frames = n; t.blk_frame = (const int32_t*)(gm + h_bf); t.f_col0 = (const int32_t*)(gm + h_c0); t.f_np = (const int32_t*)(gm + h_np);
     t.f_mask = (const uint8_t* const*)(gm + h_fmask); t.in_grid = g + g_grid; t.max_points = max_points;
+    t.cur_ptrs = resident ? (const uint8_t* const*)(gr + h_cp) : nullptr;
 
     WarpKernelArgs wa;
     memset(&wa, 0, sizeof wa);
@@ -3039,7 +3106,8 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
     wa.n_frames = n; wa.fx = cam->fx; wa.fy = cam->fy; wa.cx = cam->cx; wa.cy = cam->cy; wa.no_xcd = options().fmd_no_xcd;
     A2DKernelArgs aa;
     memset(&aa, 0, sizeof aa);
-    aa.cur_pyr = slab; aa.level = t.search_level; aa.px_xy = t.px; aa.converged = t.converged; aa.m = (int)C; aa.max_iters = d0.align2d_iters;
+    aa.cur_pyr = resident ? cur[(size_t)order[0]]->d : slab;      // (resident: not read — the workgroups go through t.cur_ptrs)
+    aa.level = t.search_level; aa.px_xy = t.px; aa.converged = t.converged; aa.m = (int)C; aa.max_iters = d0.align2d_iters;
     aa.levels = pl.levels; aa.px_level0 = 1; aa.frame = t.cand_frame; aa.n_frames = n; aa.pyr_pitch = pitch;
     for (int l = 0; l < pl.levels; ++l) aa.lv[l] = wa.lv[l];
 
@@ -3071,12 +3139,12 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         if (cnt[4 * s + 2] == 2 && !lost) { set_err(ctx, "track_frames: frame %d: the replay of the cell walk did not settle", order[(size_t)s]); return fail(DSDTM_ERR_HIP); }
     }
 #undef TRACKS_TRY
-    // ---- the frames (all or nothing) ----
-    FrameSlab* sl = new (std::nothrow) FrameSlab();
+    // ---- the frames (all or nothing; resident: the caller's own, untouched) ----
+    FrameSlab* sl = resident ? nullptr : new (std::nothrow) FrameSlab();
     std::vector<dsdtm_frame*> fr;
-    bool ok = sl != nullptr;
+    bool ok = resident || sl != nullptr;
     if (ok) { try { fr.assign(NF, nullptr); } catch (...) { ok = false; } }
-    for (int s = 0; ok && s < n; ++s) {
+    for (int s = 0; ok && !resident && s < n; ++s) {
         dsdtm_frame* f = new (std::nothrow) dsdtm_frame();
         if (!f) { ok = false; break; }
         f->owner = ctx; f->device = ctx->device; f->d = slab + (size_t)s * pitch; f->pitch = pitch; f->pl = pl; f->slab = sl;
@@ -3088,7 +3156,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         set_err(ctx, "out of host memory");
         return fail(DSDTM_ERR_NOMEM);
     }
-    sl->owner = ctx; sl->device = ctx->device; sl->d = slab; sl->bytes = slab_bytes; sl->refs.store(n);
+    if (sl) { sl->owner = ctx; sl->device = ctx->device; sl->d = slab; sl->bytes = slab_bytes; sl->refs.store(n); }
     size_t grid_at = 0;
     std::vector<size_t> grid_start(NF, 0);
     for (int f = 0; f < n; ++f) { grid_start[(size_t)f] = grid_at; grid_at += (size_t)descs[f].n_points; }
@@ -3096,7 +3164,7 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         const int f = order[(size_t)s];
         const size_t S = (size_t)s;
         dsdtm_track_result* res = &results[f];
-        res->frame = fr[S];
+        if (!resident) res->frame = fr[S];
         memcpy(res->T_run, h + h_T + S * 96, 96);
         res->n_tracked = ((const int32_t*)(h + h_nt))[s];
         memcpy(&res->stats, h + h_st + S * sizeof(dsdtm_align_stats), sizeof res->stats);

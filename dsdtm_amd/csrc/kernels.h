@@ -42,6 +42,9 @@ struct SAKernelArgs {
     // dsdtm_track_frames: pair p's reference pyramid is ref_ptrs[p] (device array of separately allocated pyramids, each
     // pyr_pitch bytes) instead of ref_pyr + p * pyr_pitch; null: the packed layout. Register kernels only.
     const uint8_t* const* ref_ptrs;
+    // dsdtm_track_frames on resident frames: pair p's current pyramid is cur_ptrs[p] instead of cur_pyr + p * pyr_pitch; null: the
+    // packed slab. Read by the pointer-table kernel only (sparse_align_reg_ptrs_kernel): the packed-layout kernels never see it.
+    const uint8_t* const* cur_ptrs;
 };
 
 // Diagnostic switches (A/B runs, tests). They exist as VARIABLES only in the diagnostic build (build.py --diag,
@@ -226,6 +229,8 @@ struct TrackArgs {
     const int32_t* blk_frame; const int32_t* f_col0; const int32_t* f_np; const uint8_t* const* f_mask;
     uint8_t* in_grid;                                 // per column: 1 = ReprojectPoint put the point into the grid
     int max_points;                                   // the largest f_np (the replay's LDS and elements per thread)
+    // resident frames (separate allocations): frame f's current pyramid is cur_ptrs[f]; null: the slab, b.cur_pyr + f * b.pyr_pitch
+    const uint8_t* const* cur_ptrs;
 };
 constexpr int TRACK_COL_GROUP = 16;   // candidates per workgroup of the track match kernels (MATCH_G of match_body.h)
 // reprojection of every local map point + FindMatchDirect for it (wa / aa: the fused FindMatchDirect kernel's arguments over the

@@ -19,9 +19,12 @@ struct MatchShared {
     __attribute__((aligned(16))) float prod[MATCH_G][192];
 };
 
-// candidates cb .. cb + nb - 1 (records in sh.c / sh.sl, written before a barrier)
+// candidates cb .. cb + nb - 1 (records in sh.c / sh.sl, written before a barrier). cur_base: the current pyramid of ALL the
+// group's candidates where the caller has resolved it (track_match_batch_kernel: a workgroup belongs to one frame); null: by the
+// candidate's frame inside the packed range b.cur_pyr.
 template <int CH>
-__device__ __forceinline__ void match_rounds(const WarpKernelArgs& a, const A2DKernelArgs& b, MatchShared<CH>& sh, int cb, int nb, int tid) {
+__device__ __forceinline__ void match_rounds(const WarpKernelArgs& a, const A2DKernelArgs& b, MatchShared<CH>& sh, int cb, int nb, int tid,
+                                             const uint8_t* cur_base = nullptr) {
     constexpr int PPL = 4, LPF = 64 / PPL, FPW = 64 / LPF;
     const int lane = tid & 63;
     const int slot = (tid >> 6) * FPW + lane / LPF, l = lane % LPF;
@@ -38,7 +41,7 @@ __device__ __forceinline__ void match_rounds(const WarpKernelArgs& a, const A2DK
         const bool valid = exists && !(lvl < 0 || lvl >= b.levels || fr < 0 || (b.frame && fr >= b.n_frames));
         if (exists && !valid && l == 0) b.converged[f] = 0;             // rejected candidate: "not converged", pixel untouched
         const LevelGeom lg = b.lv[valid ? lvl : 0];
-        const uint8_t* __restrict__ img = b.cur_pyr + (size_t)fr * b.pyr_pitch + lg.off;
+        const uint8_t* __restrict__ img = (cur_base ? cur_base : b.cur_pyr + (size_t)fr * b.pyr_pitch) + lg.off;
         const double lscale = (b.px_level0 && valid) ? (double)(1 << lvl) : 1.0;
         float u, v;
         bool converged;

@@ -1080,7 +1080,7 @@ struct RegSmem {
 };
 
 // The register kernel's body. PTRS: pair p's reference pyramid is a.ref_ptrs[p] (dsdtm_track_frames: the reference frames are
-// separate allocations) — a kernel of its own (sparse_align_reg_ptrs_kernel), so the packed-layout instantiations keep their code.
+// separate allocations), and its current pyramid a.cur_ptrs[p] where that table is given (resident frames) — a kernel of its own (sparse_align_reg_ptrs_kernel), so the packed-layout instantiations keep their code.
 template <int NPW, int PPW, bool STAMPS, bool PTRS>
 __device__ __forceinline__ void sparse_align_reg_body(const SAKernelArgs a) {
     constexpr int NP = NPW * 4;            // one partial slot per 16-lane DPP row
@@ -1249,7 +1249,8 @@ __device__ __forceinline__ void sparse_align_reg_body(const SAKernelArgs a) {
         }
         const int nf = a.n_features ? a.n_features[pair] : a.max_features;
         const uint8_t* __restrict__ ref_base = PTRS ? a.ref_ptrs[pair] : a.ref_pyr + (size_t)pair * a.pyr_pitch;
-        const uint8_t* __restrict__ cur_base = a.cur_pyr + (size_t)pair * a.pyr_pitch;
+        // (PTRS only, and there null for the packed slab: `pair` is wave-uniform, so this is one scalar load per pair)
+        const uint8_t* __restrict__ cur_base = (PTRS && a.cur_ptrs) ? a.cur_ptrs[pair] : a.cur_pyr + (size_t)pair * a.pyr_pitch;
         const FeatureRaw fraw = load_feature_raw(a, (size_t)pair * a.max_features + ltid, ltid < nf);
         unsigned long long st_pre = 0, st_pass = 0, st_h = 0, st_bar = 0;
         unsigned long long st_lvl[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // pass cycles / pass count of levels 0..3
@@ -1383,7 +1384,8 @@ __global__ __launch_bounds__(PPW * (NPW + 1) * 64) void sparse_align_reg_kernel(
     sparse_align_reg_body<NPW, PPW, STAMPS, false>(a);
 }
 
-// dsdtm_track_frames: Run for n pairs whose reference frames are separate allocations (a.ref_ptrs)
+// dsdtm_track_frames: Run for n pairs whose reference frames are separate allocations (a.ref_ptrs), and the current frames too
+// when the call runs on resident frames (a.cur_ptrs)
 template <int NPW, int PPW>
 __global__ __launch_bounds__(PPW * (NPW + 1) * 64) void sparse_align_reg_ptrs_kernel(const SAKernelArgs a) {
     sparse_align_reg_body<NPW, PPW, false, true>(a);

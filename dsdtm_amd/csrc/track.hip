@@ -157,7 +157,8 @@ __global__ __launch_bounds__(256) void track_match_kernel(const TrackArgs t, con
 
 // dsdtm_track_frames: the same for n independent frames. Every workgroup belongs to ONE frame (its columns are padded to whole
 // workgroups): it reads that frame's Run pose and count, local map and mask; the candidates carry their frame (cand_frame), so
-// the FindMatchDirect half reads the frame's pose and its pyramid in the slab (cur_pyr + frame * pyr_pitch). The XCD-aware
+// the FindMatchDirect half reads the frame's pose; its pyramid is resolved once per workgroup — the frame's entry of t.cur_ptrs
+// (resident frames: separate allocations) or its place in the slab (cur_pyr + frame * pyr_pitch). The XCD-aware
 // numbering keeps consecutive workgroups — one frame's candidates — on one L2. The first workgroup of a frame seeds the
 // frame's refinement pose.
 static_assert(TRACK_COL_GROUP == MATCH_G, "columns of the batch are padded to the match kernel's group");
@@ -171,6 +172,7 @@ __global__ __launch_bounds__(256) void track_match_batch_kernel(const TrackArgs 
         if (!a.no_xcd && lb < q * 8u) lb = (lb % 8u) * q + lb / 8u;
     }
     const int f = t.blk_frame[lb];
+    const uint8_t* const cur_base = t.cur_ptrs ? t.cur_ptrs[f] : b.cur_pyr + (size_t)f * b.pyr_pitch;   // (uniform: scalar loads)
     const int c0 = t.f_col0[f];
     const int cb = (int)lb * MATCH_G;
     const int tid = threadIdx.x;
@@ -186,7 +188,7 @@ __global__ __launch_bounds__(256) void track_match_batch_kernel(const TrackArgs 
         sh.sl[tid] = a.search_level[cb + tid];
     }
     __syncthreads();
-    match_rounds<MATCH_G>(a, b, sh, cb, nb, tid);
+    match_rounds<MATCH_G>(a, b, sh, cb, nb, tid, cur_base);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

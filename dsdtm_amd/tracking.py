@@ -131,13 +131,23 @@ def track_frame(ctx: capi.Context, cam, image, levels, last: Frame, T_seed, alig
 class TrackBatchCall:
     """One prepared dsdtm_track_frames call: n frames of n independent trackers (each described as for TrackCall: a dict of
     TrackCall's arguments), descriptors built once, `run()` the library call alone. Every frame's result equals its TrackCall's;
-    each one also carries `in_grid` (uint8 per map point: 1 = ReprojectPoint put it into the grid, i.e. into mvpLocalMapPoints)."""
+    each one also carries `in_grid` (uint8 per map point: 1 = ReprojectPoint put it into the grid, i.e. into mvpLocalMapPoints).
+    With `cur_frames` (n capi.DeviceFrame from DeviceFrame.prefetch, .from_image or an earlier batch — or a `cur_frame` in every
+    dict) the call runs in its resident mode: the new frames are already on the device, or on their way there, the images are not
+    read, the chain starts at Run, and result f's "frame" is cur_frames[f] — still the caller's."""
 
-    def __init__(self, ctx: capi.Context, cam, frames):
+    def __init__(self, ctx: capi.Context, cam, frames, cur_frames=None):
         self.ctx = ctx
+        if cur_frames is not None:
+            if len(cur_frames) != len(frames):
+                raise ValueError(f"{len(cur_frames)} resident frames for {len(frames)} frames")
+            frames = [dict(f, cur_frame=c) for f, c in zip(frames, cur_frames)]
         self.calls = [TrackCall(ctx, cam, **f) for f in frames]
         n = len(self.calls)
         self.n = n
+        self.cur_frames = [c.cur_frame for c in self.calls]
+        # (all or none; a mixture goes down as it is and the library names the first frame that differs)
+        self.resident = n > 0 and all(c is not None for c in self.cur_frames)
         self.descs = (capi.TrackDesc * max(1, n))(*[c.desc for c in self.calls])
         self.res = (capi.TrackResult * max(1, n))()
         self.max_matches = int(self.calls[0].desc.max_matches) if n else 1
@@ -150,8 +160,11 @@ class TrackBatchCall:
 
     def run_raw(self) -> int:
         """The library call alone; returns its status (the new frames' handles are in self.res[f].frame)."""
-        return self.ctx.lib.dsdtm_track_frames(self.ctx.handle, C.byref(self.cs), self.n, self.descs, self.res, self.matches.ctypes.data,
-                                               self.rn.ctypes.data, self.in_grid.ctypes.data)
+        if not self.resident:
+            for f, c in enumerate(self.cur_frames):               # (a mixture: the resident ones are named, the library refuses)
+                self.res[f].frame = c.handle.value if c is not None else None
+        return capi.track_frames(self.ctx, self.cs, self.n, self.descs, self.res, self.matches.ctypes.data, self.rn.ctypes.data,
+                                 self.in_grid.ctypes.data, frames=self.cur_frames if self.resident else None)
 
     def run(self) -> list:
         self.ctx.check(self.run_raw())
@@ -160,7 +173,8 @@ class TrackBatchCall:
             res = self.res[f]
             sm = res.summary.as_dict()
             m0 = f * self.max_matches
-            out.append(dict(frame=capi.DeviceFrame(self.ctx, C.c_void_p(res.frame)), T_run=np.array(list(res.T_run)).reshape(3, 4),
+            frame = self.cur_frames[f] if self.resident else capi.DeviceFrame(self.ctx, C.c_void_p(res.frame))
+            out.append(dict(frame=frame, T_run=np.array(list(res.T_run)).reshape(3, 4),
                             n_tracked=int(res.n_tracked), lost=bool(res.lost), stats=res.stats.as_dict(), n_in_grid=int(res.n_in_grid),
                             replay_full_scan=bool(res.replay_full_scan), matches=self.matches[m0:m0 + res.n_matches].copy(),
                             T_opt=np.array(list(res.T_opt)).reshape(3, 4), summary=sm,
@@ -169,12 +183,13 @@ class TrackBatchCall:
         return out
 
 
-def track_frames(ctx: capi.Context, cam, frames) -> list:
+def track_frames(ctx: capi.Context, cam, frames, cur_frames=None) -> list:
     """dsdtm_track_frames: `frames` is a list of dicts of track_frame's arguments after `cam` (image, levels, last, T_seed, align,
-    min_tracked, keyframes, map_points, and its keywords). Returns one track_frame result per frame, plus `in_grid`."""
+    min_tracked, keyframes, map_points, and its keywords). Returns one track_frame result per frame, plus `in_grid`.
+    cur_frames=[capi.DeviceFrame, ...]: the resident mode (see TrackBatchCall) — `image` may then be None in every dict."""
     if not frames:
         return []
-    return TrackBatchCall(ctx, cam, frames).run()
+    return TrackBatchCall(ctx, cam, frames, cur_frames).run()
 
 
 def apply_tracked_frame(cam, image, r, map_points, img_mask=None):
@@ -257,16 +272,49 @@ class MultiTracker:
         self.t = Tracker(camera, ctx, max_level, min_level, max_iters, min_tracked)
         self.cam, self.ctx = camera, self.t.ctx
         self.last_results = []
+        self._prefetched = []          # [(images, [capi.DeviceFrame])] per step, in the order prefetch() was called
+
+    def prefetch(self, images, depths=None, depth_scale: float = 5000.0):
+        """Optional, the batch twin of Tracker.prefetch: sends one step's n images (and depth maps, uint16) to the device ahead of
+        their TrackFrames — one dsdtm_frame_prefetch per sequence, each returns at once. The lockstep loop calls it for step
+        k + 1 BEFORE TrackFrames of step k; TrackFrames with the same image objects then starts at Run on those frames, and
+        last_results[i]["frame"] is sequence i's resident frame (with its depth map: .lift for a keyframe). Returns the
+        capi.DeviceFrames. At most two steps are kept: a third prefetch releases the oldest one TrackFrames never asked for."""
+        depths = depths if depths is not None else [None] * len(images)
+        if len(depths) != len(images):
+            raise ValueError(f"{len(depths)} depth maps for {len(images)} images")
+        dfs = []
+        try:
+            for im, dp in zip(images, depths):
+                dfs.append(capi.DeviceFrame.prefetch(self.ctx, im, self.t.levels, dp, depth_scale))
+        except Exception:
+            for df in dfs:
+                df.close()
+            raise
+        self._prefetched.append((list(images), dfs))
+        while len(self._prefetched) > 2:
+            for df in self._prefetched.pop(0)[1]:
+                df.close()
+        return dfs
 
     def TrackFrames(self, images, lasts, keyframes, map_points, img_masks=None):
         """Lists of n (one per sequence). Returns [(cur Frame, n_tracked, matches)] as Tracker.TrackFrame does per sequence."""
         n = len(images)
+        cur_frames = None
+        at = next((i for i, (ims, _) in enumerate(self._prefetched)
+                   if len(ims) == n and all(a is b for a, b in zip(ims, images))), None)
+        if at is not None:                     # steps prefetched before it were skipped by the caller: released
+            for _, stale in self._prefetched[:at]:
+                for df in stale:
+                    df.close()
+            cur_frames = self._prefetched[at][1]
+            del self._prefetched[:at + 1]
         img_masks = img_masks if img_masks is not None else [None] * n
         align = (self.t.levels, self.t.min_level, self.t.max_iters, int(Config.Get("Camera.Min_fts")))
         frames = [dict(image=images[i], levels=self.t.levels, last=lasts[i], T_seed=lasts[i].Get_Pose(), align=align,
                        min_tracked=self.t.min_tracked, keyframes=keyframes[i], map_points=map_points[i], mask=img_masks[i])
                   for i in range(n)]
-        rs = track_frames(self.ctx, self.cam, frames)
+        rs = track_frames(self.ctx, self.cam, frames, cur_frames)
         out = []
         for i, r in enumerate(rs):
             r["local_map_points"] = [map_points[i][j] for j in np.flatnonzero(r["in_grid"])]

@@ -487,7 +487,22 @@ int dsdtm_frame_lift(dsdtm_ctx* ctx, const dsdtm_frame* frame, const dsdtm_camer
  * (src/Feature_alignment.cpp:54-69: not bad, inside the image), i.e. the points UpdateLocalMap adds to mvpLocalMapPoints
  * (src/Tracking.cpp:299-304); all 0 for a lost frame, whose UpdateLocalMap the reference skips. Their sum is n_in_grid.
  * The returned frames are ordinary dsdtm_frames (one allocation is shared by the frames of a call and released with the last
- * of them): destroyed on their own, in any order, and usable as ref / kf by any entry that takes a frame. */
+ * of them): destroyed on their own, in any order, and usable as ref / kf by any entry that takes a frame.
+ *
+ * TWO MODES, chosen by descs[f].image — for all frames of a call or for none (a mixture: DSDTM_ERR_INVALID naming the first frame
+ * that differs from frame 0, `results` untouched):
+ *  - image mode (image != NULL everywhere): the above. results[f].frame is OUT only.
+ *  - resident mode (image == NULL everywhere): dsdtm_track_frame_on for n frames — frame f is already on the device, or on its
+ *    way there, and results[f].frame is IN/OUT: it names the frame on entry (from dsdtm_frame_prefetch, pending or not, with or
+ *    without a depth map; from dsdtm_frame_create_from_image; a frame an earlier dsdtm_track_frames call returned) and is the
+ *    same pointer on return, on success and on every error. The frame stays the caller's (to use again, to lift, to destroy);
+ *    no allocation is made, no image read (stride is ignored), and the chain starts at Run: the call's stream waits ON THE DEVICE
+ *    for the latest pending prefetch among the current, reference and key frames, never the host. Per frame every result is
+ *    that of dsdtm_track_frame_on on that frame with that descriptor, bit for bit (with the exception above for Run on several
+ *    compute units) — hence that of the image mode on the same images. A depth map the frame carries stays with it.
+ *    Checked before anything is enqueued, DSDTM_ERR_INVALID naming frame and field: results[f].frame is not NULL and belongs
+ *    to this context; its width, height and levels are descs[f]'s; no frame appears twice in the call; no frame is its own ref.
+ *    The lockstep loop of n trackers: dsdtm_frame_prefetch step k + 1 for every tracker, then this call on step k's frames. */
 #define DSDTM_TRACK_FRAMES_MAX 1024
 int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n_frames, const dsdtm_track_desc* descs,
                        dsdtm_track_result* results, dsdtm_track_match* matches, double* residual_norm, uint8_t* in_grid);

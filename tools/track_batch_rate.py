@@ -2,10 +2,18 @@
 (one call per frame: 1 context on 1 thread, and 16 contexts on 16 threads).
 
     python tools/track_batch_rate.py [--n 1,16,64,256,1024] [--reps 20] [--threads 16] [--only-batch N]
+    python tools/track_batch_rate.py --resident [--n 16,64,256] [--reps 20] [--rounds 5]
+    python tools/track_batch_rate.py --images-only [--n 16,64,256] [--reps 20]
 
 World: 640x480, 300 reference features and 900 map points per frame (8 distinct worlds, repeated). Images either in device
 memory (a torch tensor per frame) or in pinned host memory. Prints one line per configuration and a JSON summary at the end.
-`--only-batch N` runs just the device-image batch of N frames (for a rocprofv3 --kernel-trace --stats run of the stages)."""
+`--only-batch N` runs just the device-image batch of N frames (for a rocprofv3 --kernel-trace --stats run of the stages; with
+`--resident`: the resident loop of N frames).
+`--resident`: the lockstep loop on resident frames against the call on images, ALTERNATING in one process, `--rounds` times
+each: per step, dsdtm_frame_prefetch of step k + 1 for every tracker (n calls), then dsdtm_track_frames on step k's frames
+(image == NULL: the call starts at Run), then step k's frames destroyed — wall per step, the n prefetch calls and n destroys
+included; beside it the host time of the n prefetch calls alone. Median and spread (min..max) over the rounds.
+`--images-only`: the image batch alone, one line per n and memory (for A/B runs of two libraries, one process each)."""
 import argparse
 import json
 import os
@@ -65,6 +73,68 @@ def time_batch(ctx, cam, ws, n, ptrs, reps):
     return dt
 
 
+def time_resident(ctx, cam, ws, n, ptrs, reps):
+    """(wall per lockstep step, host time of the n prefetch calls of a step) on resident frames."""
+    import ctypes as C
+    call = tracking.TrackBatchCall(ctx, cam, frames_of(ws, n, [w[2].mvImg_Pyr[0] for w in ws]))
+    lib = ctx.lib
+    ims = []
+    for f in range(n):
+        im = capi.FrameImage()
+        im.gray, im.width, im.height, im.stride, im.levels = ptrs[f % len(ptrs)], cam.width, cam.height, cam.width, 5
+        ims.append(im)
+        call.descs[f].image = None
+    hnd = C.c_void_p()
+    t_pref = [0.0]
+
+    def prefetch():
+        t0 = time.perf_counter()
+        out = []
+        for f in range(n):
+            ctx.check(lib.dsdtm_frame_prefetch(ctx.handle, C.byref(ims[f]), C.byref(hnd)))
+            out.append(hnd.value)
+        t_pref[0] += time.perf_counter() - t0
+        return out
+
+    def loop(m):
+        nxt = prefetch()
+        for _ in range(m):
+            cur, nxt = nxt, prefetch()
+            for f in range(n):
+                call.res[f].frame = cur[f]
+            ctx.check(lib.dsdtm_track_frames(ctx.handle, C.byref(call.cs), n, call.descs, call.res, call.matches.ctypes.data,
+                                             call.rn.ctypes.data, call.in_grid.ctypes.data))
+            for h in cur:
+                lib.dsdtm_frame_destroy(ctx.handle, h)
+        for h in nxt:
+            lib.dsdtm_frame_destroy(ctx.handle, h)
+    loop(3)
+    t_pref[0] = 0.0
+    t0 = time.perf_counter()
+    loop(reps)
+    dt = (time.perf_counter() - t0) / reps
+    return dt, t_pref[0] / (reps + 1)
+
+
+def resident_report(ctx, cam, ws, ns, mem, reps, rounds):
+    out = {}
+    for n in ns:
+        for name, ptrs in mem:
+            img, res, pre = [], [], []
+            for _ in range(rounds):                                   # the two paths alternate
+                img.append(time_batch(ctx, cam, ws, n, ptrs, reps))
+                r, p = time_resident(ctx, cam, ws, n, ptrs, reps)
+                res.append(r); pre.append(p)
+            med = lambda v: float(np.median(v))
+            out[f"n{n}_{name}"] = dict(image_ms=med(img) * 1e3, image_ms_range=[min(img) * 1e3, max(img) * 1e3], resident_ms=med(res) * 1e3,
+                                       resident_ms_range=[min(res) * 1e3, max(res) * 1e3], prefetch_calls_ms=med(pre) * 1e3,
+                                       image_frames_per_s=n / med(img), resident_frames_per_s=n / med(res))
+            print(f"n={n:4d} {name:7s}: images {med(img) * 1e3:7.3f} ms/call ({min(img) * 1e3:.3f}..{max(img) * 1e3:.3f}) {n / med(img):8.0f} frames/s | "
+                  f"resident {med(res) * 1e3:7.3f} ms/step ({min(res) * 1e3:.3f}..{max(res) * 1e3:.3f}) {n / med(res):8.0f} frames/s, "
+                  f"of it the {n} prefetch calls on the host {med(pre) * 1e3:.3f} ms", flush=True)
+    print(json.dumps(out))
+
+
 def time_single(ctxs, cam, ws, ptrs, reps):
     calls = []
     for k, ctx in enumerate(ctxs):
@@ -96,6 +166,9 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--only-batch", type=int, default=0)
+    ap.add_argument("--resident", action="store_true")
+    ap.add_argument("--images-only", action="store_true")
+    ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
     ws = worlds()
     cam = ws[0][0]
@@ -104,6 +177,21 @@ def main():
     pin = [torch.from_numpy(np.ascontiguousarray(w[2].mvImg_Pyr[0])).pin_memory() for w in ws]
     torch.cuda.synchronize()
     dptr, pptr = [t.data_ptr() for t in dev], [t.data_ptr() for t in pin]
+    if a.only_batch and a.resident:
+        dt, pre = time_resident(ctx, cam, ws, a.only_batch, dptr, a.reps)
+        print(f"resident n={a.only_batch} device images: {dt * 1e3:.3f} ms/step, {a.only_batch / dt:.0f} frames/s")
+        return
+    if a.resident or a.images_only:
+        ns = [int(x) for x in (a.n if a.n != "1,16,64,256,1024" else "16,64,256").split(",")]
+        mem = (("device", dptr), ("pinned", pptr))
+        if a.resident:
+            resident_report(ctx, cam, ws, ns, mem, a.reps, a.rounds)
+        else:
+            for n in ns:
+                for name, ptrs in mem:
+                    dt = time_batch(ctx, cam, ws, n, ptrs, a.reps)
+                    print(f"images n={n:4d} {name:7s}: {dt * 1e3:8.3f} ms/call", flush=True)
+        return
     if a.only_batch:
         dt = time_batch(ctx, cam, ws, a.only_batch, dptr, a.reps)
         print(f"batch n={a.only_batch} device images: {dt * 1e3:.3f} ms/call, {a.only_batch / dt:.0f} frames/s")
