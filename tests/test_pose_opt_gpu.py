@@ -1,6 +1,7 @@
 """GPU side of Optimizer::PoseOptimization: the HIP kernel, through the C ABI, against
 the CPU restatement (both its Ceres-shaped QR form and the normal-equation form the kernel computes),
-the committed vectors, and the reference-shaped host class."""
+the committed vectors, and the reference-shaped host class. The batch kernels that carry two / four frames per wavefront
+(4096 frames and more) are tested in tests/test_pose_opt_rows_gpu.py."""
 import ctypes as C
 
 import numpy as np
