@@ -153,6 +153,51 @@ static void set_err(dsdtm_ctx* ctx, const char* fmt, ...) {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// A pyramid as it lies on the device: dense rows, every level at a 64-byte aligned offset
+struct PackedPyr {
+    int levels;
+    int w[DSDTM_MAX_LEVELS], h[DSDTM_MAX_LEVELS];
+    size_t off[DSDTM_MAX_LEVELS];
+    size_t bytes;
+};
+
+// The packed pyramid of an image (Frame::ComputeImagePyramid: level l is ((w + 1) / 2, (h + 1) / 2) of level l - 1); st: the strides
+static void plan_image_pyramid(int width, int height, int levels, PackedPyr* pl, int st[]) {
+    pl->levels = levels;
+    size_t o = 0;
+    for (int l = 0; l < levels; ++l) {
+        pl->w[l] = l ? (pl->w[l - 1] + 1) / 2 : width; pl->h[l] = l ? (pl->h[l - 1] + 1) / 2 : height; st[l] = pl->w[l];
+        pl->off[l] = o; o += align_up((size_t)pl->w[l] * pl->h[l], 64);
+    }
+    pl->bytes = o;
+}
+
+// `rows` rows of row_bytes from one pitch to another (one memcpy where both are dense)
+static void copy_rows(void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t row_bytes, size_t rows) {
+    if (dst_stride == row_bytes && src_stride == row_bytes) { memcpy(dst, src, row_bytes * rows); return; }
+    for (size_t y = 0; y < rows; ++y) memcpy((uint8_t*)dst + y * dst_stride, (const uint8_t*)src + y * src_stride, row_bytes);
+}
+
+// the level table of a batch descriptor whose pyramids are packed
+static void fill_levels(dsdtm_batch_desc& b, const PackedPyr& pl) {
+    b.levels = pl.levels;
+    for (int l = 0; l < pl.levels; ++l) { b.width[l] = pl.w[l]; b.height[l] = pl.h[l]; b.stride[l] = pl.w[l]; b.level_offset[l] = pl.off[l]; }
+}
+
+// behind a timeout word of `stream` (which has drained): a pair that was stopped may have left its counter word behind
+static void clear_stream_counters(dsdtm_ctx* ctx, hipStream_t stream) {
+    for (int i = 0; i < dsdtm_ctx::MAX_STREAMS; ++i)
+        if (ctx->rings[i].used && ctx->rings[i].stream == stream)
+            (void)hipMemset(ctx->d_counter + i * dsdtm_ctx::COUNTERS_PER_STREAM, 0, sizeof(unsigned) * dsdtm_ctx::COUNTERS_PER_STREAM);
+}
+
+// HIP_TRY for entries that own something until they succeed: answered by the enclosing `fail` lambda (which waits for what was enqueued and releases it)
+#define API_TRY(call)                                                                                          \
+    do {                                                                                                       \
+        hipError_t e_ = (call);                                                                                \
+        if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
+    } while (0)
+
 // ---- diagnostic switches (kernels.h: Options) — diagnostic build only ----------------------------
 // The release library has no switches: options() is a compile-time constant there, nothing reads the environment,
 // and no dsdtm_debug_* symbol exists (tests/test_capi_cpu.py checks `nm -D` and `strings`).
@@ -876,13 +921,10 @@ static int streamed_issue(dsdtm_ctx* ctx, const dsdtm_stream_desc* s, const dsdt
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool chained = s->cur_image == nullptr;
     // device pyramid layout: the one dsdtm_frame_create_from_image uses (levels 64-byte aligned, pitch 256)
-    int w[DSDTM_MAX_LEVELS], h[DSDTM_MAX_LEVELS], st[DSDTM_MAX_LEVELS];
-    size_t offl[DSDTM_MAX_LEVELS], o = 0;
-    for (int l = 0; l < s->levels; ++l) {
-        w[l] = l ? (w[l - 1] + 1) / 2 : s->width; h[l] = l ? (h[l - 1] + 1) / 2 : s->height; st[l] = w[l];
-        offl[l] = o; o += align_up((size_t)w[l] * h[l], 64);
-    }
-    const size_t pit = align_up(o, 256), img = (size_t)s->width * s->height, nf = (size_t)s->max_features;
+    PackedPyr pl;
+    int st[DSDTM_MAX_LEVELS];
+    plan_image_pyramid(s->width, s->height, s->levels, &pl, st);
+    const size_t pit = align_up(pl.bytes, 256), img = (size_t)s->width * s->height, nf = (size_t)s->max_features;
     const int n_frames = chained ? n + 1 : n;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t v = off; off = align_up(off + bytes, 256); return v; };
@@ -929,8 +971,8 @@ static int streamed_issue(dsdtm_ctx* ctx, const dsdtm_stream_desc* s, const dsdt
     const uint8_t* cur_h = chained ? nullptr : s->cur_image + (size_t)lo * s->image_pitch;
     dsdtm_batch_desc b;
     memset(&b, 0, sizeof b);
-    b.max_features = s->max_features; b.levels = s->levels; b.pyr_pitch = pit;
-    for (int l = 0; l < s->levels; ++l) { b.width[l] = w[l]; b.height[l] = h[l]; b.stride[l] = st[l]; b.level_offset[l] = offl[l]; }
+    b.max_features = s->max_features; b.pyr_pitch = pit;
+    fill_levels(b, pl);
     hipStream_t comp = ctx->stream;
     for (int j = 0; j < n_chunks; ++j) {
         const int p0 = j * chunk, p1 = p0 + chunk < n ? p0 + chunk : n;      // pairs of this chunk (shard-relative)
@@ -951,9 +993,9 @@ static int streamed_issue(dsdtm_ctx* ctx, const dsdtm_stream_desc* s, const dsdt
         HIP_TRY(ctx, hipEventRecord(ctx->copy_events[j], cs));
         HIP_TRY(ctx, hipStreamWaitEvent(comp, ctx->copy_events[j], 0));
         // Frame::ComputeImagePyramid (src/Frame.cpp:74-81) for the frames that just arrived, on the device
-        if (int rc = dsdtm_pyrdown_batch_device(ctx, d + o_ref + (size_t)f0 * pit, pit, f1 - f0, s->levels, w, h, st, offl, comp)) return rc;
+        if (int rc = dsdtm_pyrdown_batch_device(ctx, d + o_ref + (size_t)f0 * pit, pit, f1 - f0, s->levels, pl.w, pl.h, st, pl.off, comp)) return rc;
         if (!chained)
-            if (int rc = dsdtm_pyrdown_batch_device(ctx, d + o_cur + (size_t)p0 * pit, pit, p1 - p0, s->levels, w, h, st, offl, comp)) return rc;
+            if (int rc = dsdtm_pyrdown_batch_device(ctx, d + o_cur + (size_t)p0 * pit, pit, p1 - p0, s->levels, pl.w, pl.h, st, pl.off, comp)) return rc;
         b.n_pairs = p1 - p0;
         b.ref_pyr = d + o_ref + (size_t)p0 * pit; b.cur_pyr = d + o_cur + (size_t)p0 * pit;
         b.px_xy = (const float*)(d + o_px + p0 * nf * 8); b.bearing = (const double*)(d + o_be + p0 * nf * 24);
@@ -1039,13 +1081,6 @@ extern "C" int dsdtm_sparse_align_batch_streamed(dsdtm_ctx* const* ctx, int n_ct
 static int frames_consume(dsdtm_ctx* ctx, unsigned long long seq, hipStream_t stream);
 static void frames_settle(dsdtm_ctx* ctx);
 
-struct PackedPyr {
-    int levels;
-    int w[DSDTM_MAX_LEVELS], h[DSDTM_MAX_LEVELS];
-    size_t off[DSDTM_MAX_LEVELS];
-    size_t bytes;
-};
-
 static int plan_pyramid(dsdtm_ctx* ctx, const dsdtm_pyramid* p, PackedPyr* out) {
     if (!p || p->levels <= 0 || p->levels > DSDTM_MAX_LEVELS) { set_err(ctx, "bad pyramid"); return DSDTM_ERR_INVALID; }
     size_t off = 0;
@@ -1063,10 +1098,7 @@ static int plan_pyramid(dsdtm_ctx* ctx, const dsdtm_pyramid* p, PackedPyr* out) 
 
 static void pack_pyramid(const dsdtm_pyramid* p, const PackedPyr& pl, uint8_t* dst) {
     for (int l = 0; l < pl.levels; ++l) {
-        uint8_t* d = dst + pl.off[l];
-        const uint8_t* s = p->data[l];
-        if (p->stride[l] == pl.w[l]) memcpy(d, s, (size_t)pl.w[l] * pl.h[l]);
-        else for (int y = 0; y < pl.h[l]; ++y) memcpy(d + (size_t)y * pl.w[l], s + (size_t)y * p->stride[l], pl.w[l]);
+        copy_rows(dst + pl.off[l], (size_t)pl.w[l], p->data[l], (size_t)p->stride[l], (size_t)pl.w[l], (size_t)pl.h[l]);
     }
 }
 
@@ -1129,9 +1161,8 @@ static int sparse_align_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
 
     dsdtm_batch_desc b;
     memset(&b, 0, sizeof b);
-    b.n_pairs = 1; b.max_features = n_features; b.levels = pl.levels;
-    for (int l = 0; l < pl.levels; ++l) { b.width[l] = pl.w[l]; b.height[l] = pl.h[l]; b.stride[l] = pl.w[l]; b.level_offset[l] = pl.off[l]; }
-    b.pyr_pitch = pitch;
+    b.n_pairs = 1; b.max_features = n_features; b.pyr_pitch = pitch;
+    fill_levels(b, pl);
     b.ref_pyr = staged_pyr ? d + o_ref : dev_ref; b.cur_pyr = staged_pyr ? d + o_cur : dev_cur;
     b.px_xy = (const float*)(d + o_px);
     b.bearing = (const double*)(d + o_bear); b.p_world = (const double*)(d + o_pw); b.initial = d + o_ini;
@@ -1153,10 +1184,7 @@ static int sparse_align_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
         if (!*h_flag) break;
         *h_flag = 0;
         if (!multi_cu || attempt == 1 || options().no_recover) {
-            // (a pair that was stopped may have left its counter behind: the context stream's words)
-            for (int i = 0; i < dsdtm_ctx::MAX_STREAMS; ++i)
-                if (ctx->rings[i].used && ctx->rings[i].stream == ctx->stream)
-                    (void)hipMemset(ctx->d_counter + i * dsdtm_ctx::COUNTERS_PER_STREAM, 0, sizeof(unsigned) * dsdtm_ctx::COUNTERS_PER_STREAM);
+            clear_stream_counters(ctx, ctx->stream);
             set_err(ctx, multi_cu ? "sparse-align kernel: a wait for a partner workgroup timed out (re-run disabled: no_recover)"
                                   : "sparse-align kernel: intra-workgroup hand-over timed out");
             return DSDTM_ERR_HIP;
@@ -1313,19 +1341,12 @@ extern "C" int dsdtm_frame_create_from_image(dsdtm_ctx* ctx, const uint8_t* leve
     }
     PackedPyr pl;
     int st[DSDTM_MAX_LEVELS];
-    pl.levels = levels;
-    size_t o = 0;
-    for (int l = 0; l < levels; ++l) {
-        pl.w[l] = l ? (pl.w[l - 1] + 1) / 2 : width; pl.h[l] = l ? (pl.h[l - 1] + 1) / 2 : height; st[l] = pl.w[l];
-        pl.off[l] = o; o += align_up((size_t)pl.w[l] * pl.h[l], 64);
-    }
-    pl.bytes = o;
+    plan_image_pyramid(width, height, levels, &pl, st);
     if (int rc = ensure_stage(ctx, (size_t)width * height)) return rc;
     dsdtm_frame* f = nullptr;
     if (int rc = frame_alloc(ctx, pl, ctx->stream, &f)) return rc;
     uint8_t* hp = (uint8_t*)ctx->h_pinned;
-    if (stride == width) memcpy(hp, level0, (size_t)width * height);
-    else for (int y = 0; y < height; ++y) memcpy(hp + (size_t)y * width, level0 + (size_t)y * stride, width);
+    copy_rows(hp, (size_t)width, level0, (size_t)stride, (size_t)width, (size_t)height);
     // level 0 enters through a kernel on the compute stream (ingest_kernel, pyrdown.hip): no copy operation in front of the
     // pyramid kernel — the hand-over from the copy engine to the compute queue costs more than the 8 us of the copy itself
     void* hpd = nullptr;
@@ -1370,13 +1391,55 @@ __attribute__((weak)) hipError_t depth_ingest_launch(const uint16_t* src, int sr
 __attribute__((weak)) hipError_t lift_launch(const LiftArgs& args, hipStream_t stream);
 }
 
-// Where an image of the caller lives, as dsdtm_track_frame sorts it (0: ordinary host memory, 1: pinned host memory,
-// 2: this device's memory; -1: another device's).
-static int image_memory(dsdtm_ctx* ctx, const void* p) {
+// Where an image of the caller lives (0: ordinary host memory, 1: pinned host memory, 2: this device's memory; -1: another device's, *device)
+static int image_memory(dsdtm_ctx* ctx, const void* p, int* device = nullptr) {
     hipPointerAttribute_t pa_;
     if (hipPointerGetAttributes(&pa_, p) != hipSuccess) { (void)hipGetLastError(); return 0; }    // (an ordinary host pointer: not an error)
+    if (device) *device = pa_.device;
     if (pa_.type == hipMemoryTypeDevice) return pa_.device == ctx->device ? 2 : -1;
     return pa_.type == hipMemoryTypeHost ? 1 : 0;
+}
+
+// How level 0 of a caller's gray image reaches the device (dsdtm_track_frame, dsdtm_track_frames, dsdtm_frame_prefetch):
+//   STAGED        packed into pinned memory of the entry's own (the caller does, and sets `dev` to its device alias), then as IN_PLACE
+//   IN_PLACE      read by ingest_kernel (pyrdown.hip) at `dev`: contiguous, 16-byte aligned, in this device's memory or in pinned
+//                 memory the device can address (a pinned image counts as pinned only when it is contiguous: a strided one is staged)
+//   COPY_D2D      a strided or odd-address image in this device's memory: hipMemcpy2DAsync
+//   COPY_H2D      a pinned image at an odd address, or one the device cannot address: hipMemcpyAsync
+//   OTHER_DEVICE  refused, in each entry's own words; `device`: where the image lives
+enum ImageRouteKind { STAGED, IN_PLACE, COPY_D2D, COPY_H2D, OTHER_DEVICE };
+struct ImageRoute { ImageRouteKind route; const void* dev; int device; };
+// clear_unaligned: the HIP error state is cleared for an odd-address pinned image too, although nothing failed (dsdtm_track_frames
+// and dsdtm_frame_prefetch do, dsdtm_track_frame does not: kept as each was). known_mem: image_memory(ptr), where the caller has it.
+static ImageRoute route_image(dsdtm_ctx* ctx, const void* ptr, int width, int stride, bool clear_unaligned, const int* known_mem = nullptr) {
+    ImageRoute r = {STAGED, nullptr, 0};
+    const int mem = known_mem ? *known_mem : image_memory(ctx, ptr, &r.device);
+    const bool contiguous = stride == width, aligned = !(((size_t)ptr) & 15);
+    if (mem < 0) r.route = OTHER_DEVICE;
+    else if (mem == 2) { r.route = contiguous && aligned ? IN_PLACE : COPY_D2D; r.dev = contiguous && aligned ? ptr : nullptr; }
+    else if (mem == 1 && contiguous) {
+        void* p_ = nullptr;
+        r.route = COPY_H2D;
+        if (aligned && hipHostGetDevicePointer(&p_, (void*)ptr, 0) == hipSuccess) { r.route = IN_PLACE; r.dev = p_; }
+        else if (aligned || clear_unaligned) (void)hipGetLastError();
+    }
+    return r;
+}
+// What rides with the first ingest launch of a tracked call: Run's inputs and in/out words, pinned -> device
+struct RunRange { const void* src; void* dst; size_t bytes; };
+// Level 0 of `image` into dst (dense rows) by its route. run (may be NULL): moved by the same ingest launch; behind a copy-engine
+// route it gets an ingest launch of its own, with no image.
+static int enqueue_level0(dsdtm_ctx* ctx, const ImageRoute& r, const uint8_t* image, int width, int height, int stride, uint8_t* dst,
+                          const RunRange* run, hipStream_t stream) {
+    const size_t W = (size_t)width, H = (size_t)height;
+    if (r.route == COPY_D2D || r.route == COPY_H2D) {
+        if (r.route == COPY_D2D) HIP_TRY(ctx, hipMemcpy2DAsync(dst, W, image, (size_t)stride, W, H, hipMemcpyDeviceToDevice, stream));
+        else HIP_TRY(ctx, hipMemcpyAsync(dst, image, W * H, hipMemcpyHostToDevice, stream));
+        if (run) HIP_TRY(ctx, ingest_launch(nullptr, nullptr, 0, run->src, run->dst, run->bytes, stream));
+        return DSDTM_OK;
+    }
+    HIP_TRY(ctx, ingest_launch(r.dev, dst, W * H, run ? run->src : nullptr, run ? run->dst : nullptr, run ? run->bytes : 0, stream));
+    return DSDTM_OK;
 }
 
 // Frame construction (src/Frame.cpp:35-41) off the tracked frame's chain: level 0, the pyramid and the depth conversion are
@@ -1404,7 +1467,7 @@ extern "C" int dsdtm_frame_prefetch(dsdtm_ctx* ctx, const dsdtm_frame_image* im,
         if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
         if (cs != hipStreamCaptureStatusNone) { set_err(ctx, "prefetch: not inside a stream capture"); return DSDTM_ERR_INVALID; }
     }
-    const int gray_mem = image_memory(ctx, im->gray), depth_mem = im->depth ? image_memory(ctx, im->depth) : 0;
+    const int gray_mem = image_memory(ctx, im->gray), depth_mem = im->depth ? image_memory(ctx, im->depth) : 0;   // (the depth map: its memory kind only — no alignment rule, no 2-D copy)
     if (gray_mem < 0 || depth_mem < 0) { set_err(ctx, "prefetch: image->%s lives on another device than the context's (%d)", gray_mem < 0 ? "gray" : "depth", ctx->device); return DSDTM_ERR_INVALID; }
     if (!ctx->prefetch_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->prefetch_stream, hipStreamNonBlocking));
     {
@@ -1412,30 +1475,14 @@ extern "C" int dsdtm_frame_prefetch(dsdtm_ctx* ctx, const dsdtm_frame_image* im,
         if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     hipStream_t ps = ctx->prefetch_stream;
-
     PackedPyr pl;
     int st[DSDTM_MAX_LEVELS];
-    pl.levels = im->levels;
-    {
-        size_t o = 0;
-        for (int l = 0; l < pl.levels; ++l) {
-            pl.w[l] = l ? (pl.w[l - 1] + 1) / 2 : im->width; pl.h[l] = l ? (pl.h[l - 1] + 1) / 2 : im->height; st[l] = pl.w[l];
-            pl.off[l] = o; o += align_up((size_t)pl.w[l] * pl.h[l], 64);
-        }
-        pl.bytes = o;
-    }
+    plan_image_pyramid(im->width, im->height, im->levels, &pl, st);
     const size_t W = (size_t)im->width, H = (size_t)im->height, img = W * H;
     // how each image travels (the gray image as in dsdtm_track_frame): read in place by a kernel, moved by the copy engine
     // from where it is, or staged — copied into a slot of the prefetch ring now, so that the caller's buffer is free on return
-    const bool contiguous = im->stride == im->width, aligned = !(((size_t)im->gray) & 15);
-    const void* gray_dev = nullptr;                          // the gray image as a kernel sees it, where a kernel reads it in place
-    bool gray_staged = false;
-    if (gray_mem == 2) { if (contiguous && aligned) gray_dev = im->gray; }
-    else if (gray_mem == 1 && contiguous) {
-        void* p_ = nullptr;
-        if (aligned && hipHostGetDevicePointer(&p_, (void*)im->gray, 0) == hipSuccess) gray_dev = p_;
-        else (void)hipGetLastError();
-    } else gray_staged = true;
+    ImageRoute gray = route_image(ctx, im->gray, im->width, im->stride, true, &gray_mem);
+    const bool gray_staged = gray.route == STAGED;
     const uint16_t* depth_dev = nullptr;                     // the depth map as the kernel sees it
     int depth_dev_stride = im->depth_stride;
     bool depth_staged = false;
@@ -1473,35 +1520,24 @@ extern "C" int dsdtm_frame_prefetch(dsdtm_ctx* ctx, const dsdtm_frame_image* im,
         dsdtm_frame_destroy(ctx, f);
         return rc;
     };
-#define PREFETCH_TRY(call)                                                                                     \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
-    } while (0)
     uint8_t* sh = slot ? (uint8_t*)slot->h : nullptr;
     uint8_t* shd = nullptr;                                  // the slot as the device sees it
-    if (slot) { void* p_ = nullptr; PREFETCH_TRY(hipHostGetDevicePointer(&p_, slot->h, 0)); shd = (uint8_t*)p_; }
+    if (slot) { void* p_ = nullptr; API_TRY(hipHostGetDevicePointer(&p_, slot->h, 0)); shd = (uint8_t*)p_; }
     if (gray_staged) {
-        if (contiguous) memcpy(sh + s_gray, im->gray, img);
-        else for (size_t y = 0; y < H; ++y) memcpy(sh + s_gray + y * W, im->gray + y * (size_t)im->stride, W);
-        gray_dev = shd + s_gray;
+        copy_rows(sh + s_gray, W, im->gray, (size_t)im->stride, W, H);
+        gray.dev = shd + s_gray;
     }
     if (depth_staged) {
-        uint16_t* dd = (uint16_t*)(sh + s_depth);
-        if (im->depth_stride == im->width) memcpy(dd, im->depth, img * sizeof(uint16_t));
-        else for (size_t y = 0; y < H; ++y) memcpy(dd + y * W, im->depth + y * (size_t)im->depth_stride, W * sizeof(uint16_t));
+        copy_rows(sh + s_depth, W * sizeof(uint16_t), im->depth, (size_t)im->depth_stride * sizeof(uint16_t), W * sizeof(uint16_t), H);
         depth_dev = (const uint16_t*)(shd + s_depth); depth_dev_stride = im->width;
     }
     // level 0 by a kernel where a kernel can read it (ingest_kernel, pyrdown.hip), else by the copy engine (a pinned image
     // at an odd address or one the device cannot address; a strided or odd device image), then the pyramid
-    if (gray_dev) PREFETCH_TRY(ingest_launch(gray_dev, f->d, img, nullptr, nullptr, 0, ps));
-    else if (gray_mem == 2) PREFETCH_TRY(hipMemcpy2DAsync(f->d, W, im->gray, (size_t)im->stride, W, H, hipMemcpyDeviceToDevice, ps));
-    else PREFETCH_TRY(hipMemcpyAsync(f->d, im->gray, img, hipMemcpyHostToDevice, ps));
+    if (int rc = enqueue_level0(ctx, gray, im->gray, im->width, im->height, im->stride, f->d, nullptr, ps)) return fail(rc);
     if (int rc = dsdtm_pyrdown_batch_device(ctx, f->d, f->pitch, 1, pl.levels, pl.w, pl.h, st, pl.off, ps)) return fail(rc);
-    if (im->depth) PREFETCH_TRY(depth_ingest_launch(depth_dev, depth_dev_stride, f->depth, im->width, im->height, 1.0f / im->depth_scale, ctx->num_cus, ps));
+    if (im->depth) API_TRY(depth_ingest_launch(depth_dev, depth_dev_stride, f->depth, im->width, im->height, 1.0f / im->depth_scale, ctx->num_cus, ps));
     const unsigned long long seq = ctx->prefetch_seq + 1;
-    PREFETCH_TRY(hipEventRecord(ctx->prefetch_event[seq % dsdtm_ctx::PREFETCH_EVENTS], ps));
-#undef PREFETCH_TRY
+    API_TRY(hipEventRecord(ctx->prefetch_event[seq % dsdtm_ctx::PREFETCH_EVENTS], ps));
     ctx->prefetch_seq = seq;
     f->seq = seq;
     if (slot) { slot->seq = seq; ctx->prefetch_next_slot += 1; }
@@ -1829,25 +1865,22 @@ extern "C" int dsdtm_pyrdown(dsdtm_ctx* ctx, const uint8_t* level0, int width, i
     if (!ctx) return DSDTM_ERR_INVALID;
     if (!level0 || width <= 0 || height <= 0 || stride < width || levels <= 0 || levels > DSDTM_MAX_LEVELS ||
         (levels > 1 && (!out_levels || !out_stride))) { set_err(ctx, "bad argument"); return DSDTM_ERR_INVALID; }
-    int w[DSDTM_MAX_LEVELS], h[DSDTM_MAX_LEVELS], st[DSDTM_MAX_LEVELS];
-    size_t off[DSDTM_MAX_LEVELS];
-    size_t o = 0;
-    for (int l = 0; l < levels; ++l) {
-        w[l] = l ? (w[l - 1] + 1) / 2 : width; h[l] = l ? (h[l - 1] + 1) / 2 : height; st[l] = w[l];
-        off[l] = o; o += align_up((size_t)w[l] * h[l], 64);
-    }
-    const size_t pitch = align_up(o, 256);
+    PackedPyr pl;
+    int st[DSDTM_MAX_LEVELS];
+    plan_image_pyramid(width, height, levels, &pl, st);
+    const int *w = pl.w, *h = pl.h;
+    const size_t *off = pl.off, pitch = align_up(pl.bytes, 256);
     if (int rc = ensure_stage(ctx, pitch)) return rc;
     uint8_t* hp = (uint8_t*)ctx->h_pinned;
     uint8_t* d = (uint8_t*)ctx->d_stage;
-    for (int y = 0; y < height; ++y) memcpy(hp + (size_t)y * width, level0 + (size_t)y * stride, width);
+    copy_rows(hp, (size_t)width, level0, (size_t)stride, (size_t)width, (size_t)height);
     HIP_TRY(ctx, hipMemcpyAsync(d, hp, (size_t)width * height, hipMemcpyHostToDevice, ctx->stream));
     if (int rc = dsdtm_pyrdown_batch_device(ctx, d, pitch, 1, levels, w, h, st, off, ctx->stream)) return rc;
-    if (levels > 1) HIP_TRY(ctx, hipMemcpyAsync(hp + off[1], d + off[1], o - off[1], hipMemcpyDeviceToHost, ctx->stream));
+    if (levels > 1) HIP_TRY(ctx, hipMemcpyAsync(hp + off[1], d + off[1], pl.bytes - off[1], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int l = 1; l < levels; ++l) {
         if (!out_levels[l] || out_stride[l] < w[l]) { set_err(ctx, "bad output level %d", l); return DSDTM_ERR_INVALID; }
-        for (int y = 0; y < h[l]; ++y) memcpy(out_levels[l] + (size_t)y * out_stride[l], hp + off[l] + (size_t)y * w[l], w[l]);
+        copy_rows(out_levels[l], (size_t)out_stride[l], hp + off[l], (size_t)w[l], (size_t)w[l], (size_t)h[l]);
     }
     return DSDTM_OK;
 }
@@ -2390,16 +2423,7 @@ static int track_check_desc(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
     if (max_search_level < 0 || max_search_level >= d->levels) { set_err(ctx, "track: max_pyr_levels - 3 outside the pyramid"); return DSDTM_ERR_INVALID; }
     // the new frame's geometry (Frame::ComputeImagePyramid) must be the reference frame's and the keyframes'
     PackedPyr& pl = out->pl;
-    int* st = out->st;
-    pl.levels = d->levels;
-    {
-        size_t o = 0;
-        for (int l = 0; l < d->levels; ++l) {
-            pl.w[l] = l ? (pl.w[l - 1] + 1) / 2 : d->width; pl.h[l] = l ? (pl.h[l - 1] + 1) / 2 : d->height; st[l] = pl.w[l];
-            pl.off[l] = o; o += align_up((size_t)pl.w[l] * pl.h[l], 64);
-        }
-        pl.bytes = o;
-    }
+    plan_image_pyramid(d->width, d->height, d->levels, &pl, out->st);
     auto same_geometry = [&](const dsdtm_frame* f) {
         return f && f->owner == ctx && f->pl.levels == pl.levels && !memcmp(f->pl.w, pl.w, sizeof(int) * pl.levels) &&
                !memcmp(f->pl.h, pl.h, sizeof(int) * pl.levels);
@@ -2433,6 +2457,85 @@ static int track_check_desc(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
     return DSDTM_OK;
 }
 
+// ---- the staging of a tracked call, and what both entries do with it ---------------------------------------------
+// Offsets into the pinned block (h_*: host-mapped) and into the device scratch (g_*). Each entry fills it in its own order and they
+// share the names: the single call's layout is the batch's with one frame and as many columns as map points; unused members stay 0.
+struct TrackLayout {
+    size_t h_img;                                                    // staged images
+    // Run's range (what it reads, then its in/out pose, count and statistics): moved to the device in one piece
+    size_t h_run, h_px, h_bear, h_pw, h_ini, h_nf, h_tr, h_rp, h_cp, h_T, h_nt, h_st, run_bytes, run_out_bytes;
+    // the local map(s) and mask(s): one contiguous range, copied to the device in one piece
+    size_t h_map, h_mask, h_fmask, h_bf, h_c0, h_np, h_mpw, h_found, h_bad, h_off, h_okf, h_opx, h_olv, h_ob, h_Tkf, h_kfp, map_bytes;
+    size_t h_cnt, h_match, h_Topt, h_sm, h_rn, h_grid, h_total;      // results the kernels post straight into the pinned block
+    size_t g_run, g_map, g_pw, g_cell, g_px0, g_px, g_ck, g_cf, g_rpx, g_rl, g_rb, g_ib, g_sl, g_cv, g_grid, g_pob, g_pow, g_pol, g_pou,
+           g_pon, g_Topt, g_total;
+};
+
+// The arguments of the kernels behind Run — reprojection + FindMatchDirect, the replay, the pose refinement — from the layout.
+// g / hd: the device scratch and the pinned block as the device sees it; d: search parameters of every frame; columns / n_kf: over
+// all frames. The caller then sets what is its own: dsdtm_track_frame the mask and run_out_n16, dsdtm_track_frames the per-frame tables.
+static void bind_track_kernels(const TrackLayout& L, uint8_t* g, uint8_t* hd, const dsdtm_camera* cam, const dsdtm_track_desc* d,
+                               const TrackPlan& plan, int n_frames, int columns, int n_kf, const uint8_t* cur_pyr, size_t pitch,
+                               TrackArgs& t, WarpKernelArgs& wa, A2DKernelArgs& aa, PoseOptArgs& pa) {
+    const PackedPyr& pl = plan.pl;
+    uint8_t* const gr = g + L.g_run - L.h_run;          // device address of the pinned block's offset X inside Run's range: gr + X
+    const uint8_t* gm = g + L.g_map - L.h_map;          // ... inside the map range: gm + X
+    memset(&t, 0, sizeof t);
+    t.T_run = (const double*)(gr + L.h_T); t.n_tracked = (const int32_t*)(gr + L.h_nt); t.min_tracked = d->min_tracked;
+    t.run_out_dev = gr + L.h_T; t.run_out_host = hd + L.h_T;
+    t.T_kf_w = (const double*)(gm + L.h_Tkf); t.kf_ptrs = (const uint8_t* const*)(gm + L.h_kfp); t.n_kf = n_kf;
+    t.mp_world = (const double*)(gm + L.h_mpw); t.mp_found = (const int32_t*)(gm + L.h_found); t.mp_bad = gm + L.h_bad; t.n_points = columns;
+    t.obs_offset = (const int32_t*)(gm + L.h_off); t.obs_kf = (const int32_t*)(gm + L.h_okf); t.obs_px = (const float*)(gm + L.h_opx);
+    t.obs_level = (const int32_t*)(gm + L.h_olv); t.obs_bearing = (const double*)(gm + L.h_ob);
+    t.mask = nullptr; t.mask_stride = d->width;
+    t.fx = cam->fx; t.fy = cam->fy; t.cx = cam->cx; t.cy = cam->cy; t.width = cam->width; t.height = cam->height; t.levels = pl.levels;
+    t.cell_size = d->cell_size; t.grid_cols = plan.grid_cols; t.grid_rows = plan.grid_rows; t.max_matches = d->max_matches;
+    track_disc_half_widths(d->cell_size, t.disc_hw);
+    t.pw = (double*)(g + L.g_pw); t.cell = (int32_t*)(g + L.g_cell); t.px0 = (double*)(g + L.g_px0); t.px = (double*)(g + L.g_px);
+    t.cand_kf = (int32_t*)(g + L.g_ck); t.cand_frame = (int32_t*)(g + L.g_cf); t.ref_px = (float*)(g + L.g_rpx); t.ref_level = (int32_t*)(g + L.g_rl);
+    t.ref_bearing = (double*)(g + L.g_rb); t.init_blocked = g + L.g_ib; t.search_level = (int32_t*)(g + L.g_sl); t.converged = g + L.g_cv;
+    t.matches = (dsdtm_track_match*)(hd + L.h_match); t.counts = (int32_t*)(hd + L.h_cnt); t.T_opt = (double*)(g + L.g_Topt);
+    t.po_bearing = (double*)(g + L.g_pob); t.po_world = (double*)(g + L.g_pow); t.po_level = (int32_t*)(g + L.g_pol); t.po_use = g + L.g_pou;
+    t.po_n = (int32_t*)(g + L.g_pon);
+    memset(&wa, 0, sizeof wa);
+    for (int l = 0; l < pl.levels; ++l) { wa.lv[l].w = pl.w[l]; wa.lv[l].h = pl.h[l]; wa.lv[l].stride = pl.w[l]; wa.lv[l].off = (uint32_t)pl.off[l]; }
+    wa.kf_ptrs = t.kf_ptrs; wa.T_kf_w = t.T_kf_w; wa.T_cur_w_arr = t.T_run; wa.cand_frame = t.cand_frame;
+    wa.cand_kf = t.cand_kf; wa.ref_px = t.ref_px; wa.ref_level = t.ref_level; wa.ref_bearing = t.ref_bearing; wa.p_world = t.pw;
+    wa.search_level = t.search_level; wa.m = columns; wa.n_kf = n_kf; wa.max_search_level = plan.max_search_level; wa.levels = pl.levels;
+    wa.n_frames = n_frames; wa.fx = cam->fx; wa.fy = cam->fy; wa.cx = cam->cx; wa.cy = cam->cy; wa.no_xcd = options().fmd_no_xcd;
+    memset(&aa, 0, sizeof aa);
+    aa.cur_pyr = cur_pyr; aa.level = t.search_level; aa.px_xy = t.px; aa.converged = t.converged; aa.m = columns; aa.max_iters = d->align2d_iters;
+    aa.levels = pl.levels; aa.px_level0 = 1; aa.frame = t.cand_frame; aa.n_frames = n_frames; aa.pyr_pitch = pitch;
+    for (int l = 0; l < pl.levels; ++l) aa.lv[l] = wa.lv[l];
+    pa.n_frames = n_frames; pa.max_features = d->max_matches; pa.max_iterations = d->pose_opt.max_iterations;
+    pa.n_features = t.po_n; pa.bearing = t.po_bearing; pa.p_world = t.po_world; pa.level = t.po_level; pa.use = t.po_use;
+    pa.T_cur_w = t.T_opt; pa.T_mirror = (double*)(hd + L.h_Topt); pa.residual_norm = (double*)(hd + L.h_rn); pa.summary = (dsdtm_pose_opt_summary*)(hd + L.h_sm);
+    pa.force_variant = 3;                              // one wave / four waves per frame by its match count, chosen by the kernel
+}
+
+// The results of the frame in slot `slot` out of the pinned block h, behind the wait. stride: matches per frame in the block.
+// false: the replay of the frame's cell walk did not settle — nothing behind replay_full_scan is read (the caller reports it).
+static bool read_track_result(const uint8_t* h, const TrackLayout& L, size_t slot, size_t stride, int min_tracked, dsdtm_track_result* res,
+                              dsdtm_track_match* matches, double* residual_norm) {
+    memcpy(res->T_run, h + L.h_T + slot * 96, 96);
+    res->n_tracked = ((const int32_t*)(h + L.h_nt))[slot];
+    memcpy(&res->stats, h + L.h_st + slot * sizeof(dsdtm_align_stats), sizeof res->stats);
+    res->lost = res->n_tracked < min_tracked ? 1 : 0;
+    const int32_t* cnt = (const int32_t*)(h + L.h_cnt) + 4 * slot;
+    res->n_in_grid = cnt[0];
+    res->n_matches = res->lost ? 0 : cnt[1];
+    res->replay_full_scan = cnt[2] == 1 ? 1 : 0;
+    if (cnt[2] == 2 && !res->lost) return false;
+    if (res->lost) memcpy(res->T_opt, res->T_run, 96);
+    else {
+        memcpy(res->T_opt, h + L.h_Topt + slot * 96, 96);
+        memcpy(&res->summary, h + L.h_sm + slot * sizeof(dsdtm_pose_opt_summary), sizeof res->summary);
+        if (res->n_matches > 0) memcpy(matches, h + L.h_match + slot * stride * sizeof(dsdtm_track_match), (size_t)res->n_matches * sizeof(dsdtm_track_match));
+        if (res->summary.n_residual_blocks > 0) memcpy(residual_norm, h + L.h_rn + slot * stride * 8, (size_t)res->summary.n_residual_blocks * 8);
+    }
+    return true;
+}
+
 // ---- one tracked frame in ONE submission (src/Tracking.cpp:199-256) ------------------------------
 // new frame -> Run -> ReprojectPoint + Get_ClosetObs for every local map point -> FindMatchDirect for all of them -> the cell
 // walk of SearchLocalPoints replayed on the device -> PoseOptimization, enqueued back to back on the context's stream; the host
@@ -2441,6 +2544,7 @@ static int track_check_desc(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
 // works on device memory and the few results are written (posted) to the pinned block by whichever kernel has them first.
 // cur == NULL: dsdtm_track_frame — the new frame is made here from d->image. cur != NULL: dsdtm_track_frame_on — the frame is
 // already on the device (or on its way there: the stream waits for its event); the chain starts at Run.
+// (No heap allocation on this path: its state is on the stack.)
 static int track_frame_impl(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm_track_desc* d, dsdtm_frame* cur, dsdtm_track_result* res,
                             dsdtm_track_match* matches, double* residual_norm) {
     memset(res, 0, sizeof *res);
@@ -2465,44 +2569,39 @@ static int track_frame_impl(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
         if (cur->seq > plan.frames_seq) plan.frames_seq = cur->seq;
     }
     const PackedPyr& pl = plan.pl;
-    const int* st = plan.st;
-    const int max_search_level = plan.max_search_level, M = d->n_points, nnz = plan.nnz;
-    const int grid_rows = plan.grid_rows, grid_cols = plan.grid_cols;
+    const int M = d->n_points, nnz = plan.nnz;
     const size_t img = (size_t)d->width * d->height, nf = (size_t)d->n_ref_features, Mz = (size_t)M, NZ = (size_t)nnz,
                  MM = (size_t)d->max_matches, NK = (size_t)d->n_kf;
-    // ---- the pinned block (host-mapped): inputs, then results ----
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t h_img = take(img);
-    // (Run's range: what it reads, then its in/out pose, count and statistics — moved to the device in one piece, see below)
-    const size_t h_run = o;
-    const size_t h_bear = take(nf * 24), h_pw = take(nf * 24), h_tr = take(96), h_px = take(nf * 8), h_ini = take(nf);
-    const size_t h_T = take(96), h_nt = take(4), h_st = take(sizeof(dsdtm_align_stats));
-    const size_t run_bytes = o - h_run, run_out_bytes = o - h_T;
-    // (the local map and the mask: one contiguous range, copied to the device in one piece)
-    const size_t h_map = o;
-    const size_t h_mask = take(d->mask ? img : 0);
-    const size_t h_mpw = take(Mz * 24), h_found = take(Mz * 4), h_bad = take(Mz), h_off = take((Mz + 1) * 4), h_okf = take(NZ * 4),
-                 h_opx = take(NZ * 8), h_olv = take(NZ * 4), h_ob = take(NZ * 24), h_Tkf = take(NK * 96), h_kfp = take(NK * sizeof(void*));
-    const size_t map_bytes = o - h_map;
-    const size_t h_cnt = take(64), h_match = take(MM * sizeof(dsdtm_track_match)), h_Topt = take(96),
-                 h_sm = take(sizeof(dsdtm_pose_opt_summary)), h_rn = take(MM * 8);
-    const size_t h_total = o;
-    // ---- device scratch ----
-    o = 0;
-    const size_t g_run = take(run_bytes), g_map = take(map_bytes), g_pw = take(Mz * 24), g_cell = take(Mz * 4),
-                 g_px0 = take(Mz * 16), g_px = take(Mz * 16), g_ck = take(Mz * 4), g_cf = take(Mz * 4), g_rp = take(Mz * 8),
-                 g_rl = take(Mz * 4), g_rb = take(Mz * 24), g_ib = take(Mz), g_sl = take(Mz * 4), g_cv = take(Mz),
-                 g_pob = take(MM * 24), g_pow = take(MM * 24), g_pol = take(MM * 4), g_pou = take(MM), g_pon = take(4), g_Topt = take(96);
-    const size_t g_total = o;
-    if (int rc = ensure_stage(ctx, h_total > g_total ? h_total : g_total)) return rc;
+    TrackLayout L = {};
+    {
+        size_t o = 0;
+        auto take = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
+        L.h_img = take(img);
+        L.h_run = o;
+        L.h_bear = take(nf * 24); L.h_pw = take(nf * 24); L.h_tr = take(96); L.h_px = take(nf * 8); L.h_ini = take(nf);
+        L.h_T = take(96); L.h_nt = take(4); L.h_st = take(sizeof(dsdtm_align_stats));
+        L.run_bytes = o - L.h_run; L.run_out_bytes = o - L.h_T;
+        L.h_map = o;
+        L.h_mask = take(d->mask ? img : 0);
+        L.h_mpw = take(Mz * 24); L.h_found = take(Mz * 4); L.h_bad = take(Mz); L.h_off = take((Mz + 1) * 4); L.h_okf = take(NZ * 4);
+        L.h_opx = take(NZ * 8); L.h_olv = take(NZ * 4); L.h_ob = take(NZ * 24); L.h_Tkf = take(NK * 96); L.h_kfp = take(NK * sizeof(void*));
+        L.map_bytes = o - L.h_map;
+        L.h_cnt = take(64); L.h_match = take(MM * sizeof(dsdtm_track_match)); L.h_Topt = take(96); L.h_sm = take(sizeof(dsdtm_pose_opt_summary));
+        L.h_rn = take(MM * 8); L.h_total = o;
+        o = 0;
+        L.g_run = take(L.run_bytes); L.g_map = take(L.map_bytes); L.g_pw = take(Mz * 24); L.g_cell = take(Mz * 4);
+        L.g_px0 = take(Mz * 16); L.g_px = take(Mz * 16); L.g_ck = take(Mz * 4); L.g_cf = take(Mz * 4); L.g_rpx = take(Mz * 8);
+        L.g_rl = take(Mz * 4); L.g_rb = take(Mz * 24); L.g_ib = take(Mz); L.g_sl = take(Mz * 4); L.g_cv = take(Mz);
+        L.g_pob = take(MM * 24); L.g_pow = take(MM * 24); L.g_pol = take(MM * 4); L.g_pou = take(MM); L.g_pon = take(4); L.g_Topt = take(96);
+        L.g_total = o;
+    }
+    if (int rc = ensure_stage(ctx, L.h_total > L.g_total ? L.h_total : L.g_total)) return rc;
     uint8_t* h = (uint8_t*)ctx->h_pinned;
     uint8_t* g = (uint8_t*)ctx->d_stage;
     void* hd_ = nullptr;
     HIP_TRY(ctx, hipHostGetDevicePointer(&hd_, ctx->h_pinned, 0));
     uint8_t* hd = (uint8_t*)hd_;                       // the pinned block as the device sees it
     hipStream_t stream = ctx->stream;
-
     dsdtm_frame* f = cur;
     if (!cur) { if (int rc = frame_alloc(ctx, pl, stream, &f)) return rc; }
     auto fail = [&](int rc) {
@@ -2511,79 +2610,52 @@ static int track_frame_impl(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
         if (!cur) dsdtm_frame_destroy(ctx, f);          // (a frame the caller handed in stays the caller's)
         return rc;
     };
-#define TRACK_TRY(call)                                                                                        \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
-    } while (0)
-
     // 1. the new frame: level 0 crosses the link, the pyramid is built on the device (src/Frame.cpp:35-41, :74-81); with it
     //    what Run(cur, ref) reads and its in/out pose: ONE kernel (ingest_kernel, pyrdown.hip) on the compute stream reads both
     //    from host-mapped pinned memory — no copy operation in front of the first kernel (the hand-over from the copy engine
     //    costs 7-8 us), and Run reads its 57 bytes per feature from HBM instead of over the link.
-    // (an image the caller keeps in pinned memory — hipHostMalloc / hipHostRegister, e.g. the capture buffer — is read straight
-    // from there; anything else is staged through the context's pinned block first: 5-15 us of host memcpy for 640x480)
-    // (an image that already lives in this device's memory — a capture or decode pipeline on the GPU — is read from there by the same
-    // kernel, or by a device-to-device copy when it is strided or not 16-byte aligned)
-    bool pinned_image = false, device_image = false;
+    // (an image in pinned memory — e.g. the capture buffer — or in this device's memory is read from there; anything else is
+    // staged through the context's pinned block first: 5-15 us of host memcpy for 640x480. The routes: ImageRoute)
+    ImageRoute route = {IN_PLACE, nullptr, 0};
     if (!cur) {
-        hipPointerAttribute_t pa_;
-        if (hipPointerGetAttributes(&pa_, d->image) == hipSuccess) {
-            device_image = pa_.type == hipMemoryTypeDevice;
-            pinned_image = pa_.type == hipMemoryTypeHost && d->stride == d->width;
-            if (device_image && pa_.device != ctx->device) { set_err(ctx, "track: the image lives on device %d, the context on %d", pa_.device, ctx->device); return fail(DSDTM_ERR_INVALID); }
-        } else (void)hipGetLastError();                // (an ordinary host pointer: not an error)
-    }
-    const void* img_dev = nullptr;                     // the image as the device sees it
-    if (cur) {
-        // (nothing to bring in: the frame is resident, or its prefetch is what the stream waits for below)
-    } else if (device_image) {
-        if (d->stride == d->width && !(((size_t)d->image) & 15)) img_dev = d->image;
-    } else if (pinned_image && !(((size_t)d->image) & 15)) {
-        void* p_ = nullptr;
-        if (hipHostGetDevicePointer(&p_, (void*)d->image, 0) == hipSuccess) img_dev = p_;
-        else (void)hipGetLastError();
-    }
-    if (!cur && !pinned_image && !device_image) {
-        if (d->stride == d->width) memcpy(h + h_img, d->image, img);
-        else for (int y = 0; y < d->height; ++y) memcpy(h + h_img + (size_t)y * d->width, d->image + (size_t)y * d->stride, (size_t)d->width);
-        img_dev = hd + h_img;
+        route = route_image(ctx, d->image, d->width, d->stride, false);
+        if (route.route == OTHER_DEVICE) { set_err(ctx, "track: the image lives on device %d, the context on %d", route.device, ctx->device); return fail(DSDTM_ERR_INVALID); }
+        if (route.route == STAGED) {
+            copy_rows(h + L.h_img, (size_t)d->width, d->image, (size_t)d->stride, (size_t)d->width, (size_t)d->height);
+            route.dev = hd + L.h_img;
+        }
     }
     if (nf) {
-        memcpy(h + h_bear, d->ref_bearing, nf * 24);
-        memcpy(h + h_pw, d->ref_p_world, nf * 24);
-        memcpy(h + h_px, d->ref_px_xy, nf * 8);
-        memcpy(h + h_ini, d->ref_initial, nf);
+        memcpy(h + L.h_bear, d->ref_bearing, nf * 24); memcpy(h + L.h_pw, d->ref_p_world, nf * 24);
+        memcpy(h + L.h_px, d->ref_px_xy, nf * 8); memcpy(h + L.h_ini, d->ref_initial, nf);
     }
-    memcpy(h + h_tr, d->T_ref_w, 96);
+    memcpy(h + L.h_tr, d->T_ref_w, 96);
     auto seed_run = [&]() {
-        memcpy(h + h_T, d->T_seed, 96);                              // cur->Set_Pose(last->Get_Pose()) (src/Tracking.cpp:201)
-        memset(h + h_nt, 0, 4); memset(h + h_st, 0, sizeof(dsdtm_align_stats));
+        memcpy(h + L.h_T, d->T_seed, 96);                            // cur->Set_Pose(last->Get_Pose()) (src/Tracking.cpp:201)
+        memset(h + L.h_nt, 0, 4); memset(h + L.h_st, 0, sizeof(dsdtm_align_stats));
     };
     seed_run();
     if (int rc = frames_consume(ctx, plan.frames_seq, stream)) return fail(rc);      // pending frames among ref / kf / cur
-    if (cur) TRACK_TRY(ingest_launch(nullptr, nullptr, 0, hd + h_run, g + g_run, run_bytes, stream));   // Run's range only
-    else if (img_dev) TRACK_TRY(ingest_launch(img_dev, f->d, img, hd + h_run, g + g_run, run_bytes, stream));
-    else {      // (a pinned image the device cannot address, or one that is not 16-byte aligned; a strided or odd device image: the copy engine)
-        if (device_image) TRACK_TRY(hipMemcpy2DAsync(f->d, (size_t)d->width, d->image, (size_t)d->stride, (size_t)d->width, (size_t)d->height, hipMemcpyDeviceToDevice, stream));
-        else TRACK_TRY(hipMemcpyAsync(f->d, pinned_image ? (const void*)d->image : (const void*)(h + h_img), img, hipMemcpyHostToDevice, stream));
-        TRACK_TRY(ingest_launch(nullptr, nullptr, 0, hd + h_run, g + g_run, run_bytes, stream));
+    const RunRange run_range = {hd + L.h_run, g + L.g_run, L.run_bytes};
+    if (cur) API_TRY(ingest_launch(nullptr, nullptr, 0, run_range.src, run_range.dst, run_range.bytes, stream));   // Run's range only
+    else {
+        if (int rc = enqueue_level0(ctx, route, d->image, d->width, d->height, d->stride, f->d, &run_range, stream)) return fail(rc);
+        if (int rc = dsdtm_pyrdown_batch_device(ctx, f->d, f->pitch, 1, pl.levels, pl.w, pl.h, plan.st, pl.off, stream)) return fail(rc);
     }
-    if (!cur) { if (int rc = dsdtm_pyrdown_batch_device(ctx, f->d, f->pitch, 1, pl.levels, pl.w, pl.h, st, pl.off, stream)) return fail(rc); }
 
     // 2. Run(cur, ref) on the device copy of its range
     // Run() (:34-38): too few features -> 0, the pose untouched. Decided on the host: no launch.
     const bool run = d->n_ref_features >= d->align.min_fts && d->align.max_level - 1 >= d->align.min_level && d->n_ref_features > 0;
-    uint8_t* const gr = g + g_run - h_run;              // device address of the pinned block's offset X inside Run's range: gr + X
+    uint8_t* const gr = g + L.g_run - L.h_run;          // device address of the pinned block's offset X inside Run's range: gr + X
     dsdtm_batch_desc b;
     memset(&b, 0, sizeof b);
-    b.n_pairs = 1; b.max_features = d->n_ref_features; b.levels = pl.levels;
-    for (int l = 0; l < pl.levels; ++l) { b.width[l] = pl.w[l]; b.height[l] = pl.h[l]; b.stride[l] = pl.w[l]; b.level_offset[l] = pl.off[l]; }
+    b.n_pairs = 1; b.max_features = d->n_ref_features;
+    fill_levels(b, pl);
     b.pyr_pitch = d->ref->pitch;
     b.ref_pyr = d->ref->d; b.cur_pyr = f->d;
-    b.px_xy = (const float*)(gr + h_px); b.bearing = (const double*)(gr + h_bear); b.p_world = (const double*)(gr + h_pw);
-    b.initial = gr + h_ini; b.T_ref_w = (const double*)(gr + h_tr); b.T_cur_w = (double*)(gr + h_T);
-    b.n_tracked = (int32_t*)(gr + h_nt); b.stats = (dsdtm_align_stats*)(gr + h_st);
+    b.px_xy = (const float*)(gr + L.h_px); b.bearing = (const double*)(gr + L.h_bear); b.p_world = (const double*)(gr + L.h_pw);
+    b.initial = gr + L.h_ini; b.T_ref_w = (const double*)(gr + L.h_tr); b.T_cur_w = (double*)(gr + L.h_T);
+    b.n_tracked = (int32_t*)(gr + L.h_nt); b.stats = (dsdtm_align_stats*)(gr + L.h_st);
     if (d->ref->pitch != f->pitch) { set_err(ctx, "track: pyramid pitches differ"); return fail(DSDTM_ERR_INVALID); }
 
     // 3. the local map, packed once (the retry below re-uses it)
@@ -2591,57 +2663,24 @@ static int track_frame_impl(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
     auto pack_map = [&]() {
         if (packed_map) return;
         packed_map = true;
-        if (d->mask) for (int y = 0; y < d->height; ++y) memcpy(h + h_mask + (size_t)y * d->width, d->mask + (size_t)y * d->mask_stride, (size_t)d->width);
+        if (d->mask) copy_rows(h + L.h_mask, (size_t)d->width, d->mask, (size_t)d->mask_stride, (size_t)d->width, (size_t)d->height);
         if (M > 0) {
-            memcpy(h + h_mpw, d->mp_world, Mz * 24); memcpy(h + h_found, d->mp_found, Mz * 4); memcpy(h + h_bad, d->mp_bad, Mz);
-            memcpy(h + h_off, d->obs_offset, (Mz + 1) * 4);
-        } else memset(h + h_off, 0, 4);
+            memcpy(h + L.h_mpw, d->mp_world, Mz * 24); memcpy(h + L.h_found, d->mp_found, Mz * 4); memcpy(h + L.h_bad, d->mp_bad, Mz);
+            memcpy(h + L.h_off, d->obs_offset, (Mz + 1) * 4);
+        } else memset(h + L.h_off, 0, 4);
         if (nnz > 0) {
-            memcpy(h + h_okf, d->obs_kf, NZ * 4); memcpy(h + h_opx, d->obs_px, NZ * 8); memcpy(h + h_olv, d->obs_level, NZ * 4);
-            memcpy(h + h_ob, d->obs_bearing, NZ * 24);
+            memcpy(h + L.h_okf, d->obs_kf, NZ * 4); memcpy(h + L.h_opx, d->obs_px, NZ * 8); memcpy(h + L.h_olv, d->obs_level, NZ * 4);
+            memcpy(h + L.h_ob, d->obs_bearing, NZ * 24);
         }
-        if (d->n_kf > 0) memcpy(h + h_Tkf, d->T_kf_w, NK * 96);
-        for (int k = 0; k < d->n_kf; ++k) ((const uint8_t**)(h + h_kfp))[k] = d->kf[k]->d;
+        if (d->n_kf > 0) memcpy(h + L.h_Tkf, d->T_kf_w, NK * 96);
+        for (int k = 0; k < d->n_kf; ++k) ((const uint8_t**)(h + L.h_kfp))[k] = d->kf[k]->d;
     };
 
-    TrackArgs t;
-    memset(&t, 0, sizeof t);
-    t.T_run = (const double*)(gr + h_T); t.n_tracked = (const int32_t*)(gr + h_nt); t.min_tracked = d->min_tracked;
-    t.run_out_dev = gr + h_T; t.run_out_host = hd + h_T; t.run_out_n16 = (int)(run_out_bytes / 16);
-    const uint8_t* gm = g + g_map - h_map;                // the device copy of the map range: same offsets as in the pinned block
-    t.T_kf_w = (const double*)(gm + h_Tkf); t.kf_ptrs = (const uint8_t* const*)(gm + h_kfp); t.n_kf = d->n_kf;
-    t.mp_world = (const double*)(gm + h_mpw); t.mp_found = (const int32_t*)(gm + h_found); t.mp_bad = gm + h_bad; t.n_points = M;
-    t.obs_offset = (const int32_t*)(gm + h_off); t.obs_kf = (const int32_t*)(gm + h_okf); t.obs_px = (const float*)(gm + h_opx);
-    t.obs_level = (const int32_t*)(gm + h_olv); t.obs_bearing = (const double*)(gm + h_ob);
-    t.mask = d->mask ? gm + h_mask : nullptr; t.mask_stride = d->width;
-    t.fx = cam->fx; t.fy = cam->fy; t.cx = cam->cx; t.cy = cam->cy; t.width = cam->width; t.height = cam->height; t.levels = pl.levels;
-    t.cell_size = d->cell_size; t.grid_cols = grid_cols; t.grid_rows = grid_rows; t.max_matches = d->max_matches;
-    track_disc_half_widths(d->cell_size, t.disc_hw);
-    t.pw = (double*)(g + g_pw); t.cell = (int32_t*)(g + g_cell); t.px0 = (double*)(g + g_px0); t.px = (double*)(g + g_px);
-    t.cand_kf = (int32_t*)(g + g_ck); t.cand_frame = (int32_t*)(g + g_cf); t.ref_px = (float*)(g + g_rp); t.ref_level = (int32_t*)(g + g_rl);
-    t.ref_bearing = (double*)(g + g_rb); t.init_blocked = g + g_ib; t.search_level = (int32_t*)(g + g_sl); t.converged = g + g_cv;
-    t.matches = (dsdtm_track_match*)(hd + h_match); t.counts = (int32_t*)(hd + h_cnt); t.T_opt = (double*)(g + g_Topt);
-    t.po_bearing = (double*)(g + g_pob); t.po_world = (double*)(g + g_pow); t.po_level = (int32_t*)(g + g_pol); t.po_use = g + g_pou;
-    t.po_n = (int32_t*)(g + g_pon);
-
-    WarpKernelArgs wa;
-    memset(&wa, 0, sizeof wa);
-    for (int l = 0; l < pl.levels; ++l) { wa.lv[l].w = pl.w[l]; wa.lv[l].h = pl.h[l]; wa.lv[l].stride = pl.w[l]; wa.lv[l].off = (uint32_t)pl.off[l]; }
-    wa.kf_ptrs = t.kf_ptrs; wa.T_kf_w = t.T_kf_w; wa.T_cur_w_arr = t.T_run; wa.cand_frame = t.cand_frame;
-    wa.cand_kf = t.cand_kf; wa.ref_px = t.ref_px; wa.ref_level = t.ref_level; wa.ref_bearing = t.ref_bearing; wa.p_world = t.pw;
-    wa.search_level = t.search_level; wa.m = M; wa.n_kf = d->n_kf; wa.max_search_level = max_search_level; wa.levels = pl.levels;
-    wa.n_frames = 1; wa.fx = cam->fx; wa.fy = cam->fy; wa.cx = cam->cx; wa.cy = cam->cy; wa.no_xcd = options().fmd_no_xcd;
-    A2DKernelArgs aa;
-    memset(&aa, 0, sizeof aa);
-    aa.cur_pyr = f->d; aa.level = t.search_level; aa.px_xy = t.px; aa.converged = t.converged; aa.m = M; aa.max_iters = d->align2d_iters;
-    aa.levels = pl.levels; aa.px_level0 = 1; aa.frame = t.cand_frame; aa.n_frames = 1; aa.pyr_pitch = f->pitch;
-    for (int l = 0; l < pl.levels; ++l) aa.lv[l] = wa.lv[l];
-
-    PoseOptArgs pa;
-    pa.n_frames = 1; pa.max_features = d->max_matches; pa.max_iterations = d->pose_opt.max_iterations;
-    pa.n_features = t.po_n; pa.bearing = t.po_bearing; pa.p_world = t.po_world; pa.level = t.po_level; pa.use = t.po_use;
-    pa.T_cur_w = t.T_opt; pa.T_mirror = (double*)(hd + h_Topt); pa.residual_norm = (double*)(hd + h_rn); pa.summary = (dsdtm_pose_opt_summary*)(hd + h_sm);
-
+    TrackArgs t; WarpKernelArgs wa; A2DKernelArgs aa; PoseOptArgs pa;
+    bind_track_kernels(L, g, hd, cam, d, plan, 1, M, d->n_kf, f->d, f->pitch, t, wa, aa, pa);
+    t.mask = d->mask ? g + L.g_map - L.h_map + L.h_mask : nullptr;
+    // (Run's pose, count and statistics reach the pinned block by the match kernel's posted writes: no copy operation on the chain)
+    t.run_out_n16 = (int)(L.run_out_bytes / 16);
     volatile unsigned* h_flag = ctx->h_flags + dsdtm_ctx::FLAG_SINGLE;
     *h_flag = 0;
     LaunchMode mode;
@@ -2650,36 +2689,33 @@ static int track_frame_impl(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
         bool multi_cu = false;
         if (attempt) {                                               // once more: Run's range again, from the seed
             seed_run();
-            TRACK_TRY(ingest_launch(nullptr, nullptr, 0, hd + h_run, g + g_run, run_bytes, stream));
+            API_TRY(ingest_launch(nullptr, nullptr, 0, run_range.src, run_range.dst, run_range.bytes, stream));
         }
-        memset(h + h_cnt, 0, 64); memset(h + h_sm, 0, sizeof(dsdtm_pose_opt_summary));
+        memset(h + L.h_cnt, 0, 64); memset(h + L.h_sm, 0, sizeof(dsdtm_pose_opt_summary));
         if (run) { if (int rc = launch_batch(ctx, &b, cam, &d->align, stream, mode, &multi_cu)) return fail(rc); }
         if (!packed_map) {
             // the local map does not depend on Run: it is packed and copied up on a second stream WHILE Run runs (its reads —
             // observation -> keyframe pose -> reference feature — are dependent chains: from host-mapped memory they cost the
             // reprojection 16 us, from HBM 4)
             pack_map();
-            if (!ctx->copy_stream[0]) TRACK_TRY(hipStreamCreateWithFlags(&ctx->copy_stream[0], hipStreamNonBlocking));
-            TRACK_TRY(hipMemcpyAsync(g + g_map, h + h_map, map_bytes, hipMemcpyHostToDevice, ctx->copy_stream[0]));
+            if (!ctx->copy_stream[0]) API_TRY(hipStreamCreateWithFlags(&ctx->copy_stream[0], hipStreamNonBlocking));
+            API_TRY(hipMemcpyAsync(g + L.g_map, h + L.h_map, L.map_bytes, hipMemcpyHostToDevice, ctx->copy_stream[0]));
             // (waited for by the HOST, while Run runs: a device-side event wait costs the stream a 6-us bubble in front of the
             // next kernel; the kernels behind Run are still enqueued long before Run ends)
-            TRACK_TRY(hipStreamSynchronize(ctx->copy_stream[0]));
+            API_TRY(hipStreamSynchronize(ctx->copy_stream[0]));
         }
         // 4. ReprojectPoint + Get_ClosetObs for every point; FindMatchDirect for every point that passed; the cell walk; the
         //    features of the matches; PoseOptimization on them — the instantiation picked on the device by the match count,
         //    as dsdtm_pose_optimization picks it on the host (same arithmetic, same bits as the four-call chain)
-        TRACK_TRY(track_match_launch(t, wa, aa, stream));
-        TRACK_TRY(track_replay_launch(t, stream));
-        pa.force_variant = 3;                                      // one wave / four waves by the match count, chosen by the kernel
-        TRACK_TRY(pose_opt_launch(pa, stream));
-        TRACK_TRY(hipStreamSynchronize(stream));
+        API_TRY(track_match_launch(t, wa, aa, stream));
+        API_TRY(track_replay_launch(t, stream));
+        API_TRY(pose_opt_launch(pa, stream));
+        API_TRY(hipStreamSynchronize(stream));
         frames_settle(ctx);
         if (!*h_flag) break;
         *h_flag = 0;
         if (!multi_cu || attempt == 1 || options().no_recover) {
-            for (int i = 0; i < dsdtm_ctx::MAX_STREAMS; ++i)
-                if (ctx->rings[i].used && ctx->rings[i].stream == ctx->stream)
-                    (void)hipMemset(ctx->d_counter + i * dsdtm_ctx::COUNTERS_PER_STREAM, 0, sizeof(unsigned) * dsdtm_ctx::COUNTERS_PER_STREAM);
+            clear_stream_counters(ctx, ctx->stream);
             set_err(ctx, multi_cu ? "sparse-align kernel: a wait for a partner workgroup timed out (re-run disabled: no_recover)"
                                   : "sparse-align kernel: intra-workgroup hand-over timed out");
             return fail(DSDTM_ERR_HIP);
@@ -2687,24 +2723,9 @@ static int track_frame_impl(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
         mode.one_cu = true;                                          // Run cannot fail for scheduling reasons: once more, on one compute unit
         ctx->recovered += 1;
     }
-#undef TRACK_TRY
     res->frame = f;
-    memcpy(res->T_run, h + h_T, 96);
-    res->n_tracked = *(const int32_t*)(h + h_nt);
-    memcpy(&res->stats, h + h_st, sizeof res->stats);
-    res->lost = res->n_tracked < d->min_tracked ? 1 : 0;
-    const int32_t* cnt = (const int32_t*)(h + h_cnt);
-    res->n_in_grid = cnt[0];
-    res->n_matches = res->lost ? 0 : cnt[1];
-    res->replay_full_scan = cnt[2] == 1 ? 1 : 0;
-    if (cnt[2] == 2 && !res->lost) { set_err(ctx, "track: the replay of the cell walk did not settle"); if (!cur) dsdtm_frame_destroy(ctx, f); res->frame = nullptr; return DSDTM_ERR_HIP; }
-    if (res->lost) {
-        memcpy(res->T_opt, res->T_run, 96);
-    } else {
-        memcpy(res->T_opt, h + h_Topt, 96);
-        memcpy(&res->summary, h + h_sm, sizeof res->summary);
-        if (res->n_matches > 0) memcpy(matches, h + h_match, (size_t)res->n_matches * sizeof(dsdtm_track_match));
-        if (res->summary.n_residual_blocks > 0) memcpy(residual_norm, h + h_rn, (size_t)res->summary.n_residual_blocks * 8);
+    if (!read_track_result(h, L, 0, MM, d->min_tracked, res, matches, residual_norm)) {
+        set_err(ctx, "track: the replay of the cell walk did not settle"); if (!cur) dsdtm_frame_destroy(ctx, f); res->frame = nullptr; return DSDTM_ERR_HIP;
     }
     return DSDTM_OK;
 }
@@ -2740,6 +2761,7 @@ extern "C" int dsdtm_track_frame_on(dsdtm_ctx* ctx, const dsdtm_camera* cam, con
 // the latest prefetch among all frames named. The frames are separate allocations in the caller's order, so Run and the
 // FindMatchDirect kernel find slot s's current pyramid through a table (cur_ptrs, in Run's range beside ref_ptrs). The frames
 // stay the caller's: results[f].frame is the same pointer on return, on success and on every failure.
+// The entry is a sequence of phases (tracks_*), each with one job; TrackBatch is what they hand on.
 static int track_band(const dsdtm_track_desc* d) {
     const bool run = d->n_ref_features >= d->align.min_fts && d->align.max_level - 1 >= d->align.min_level && d->n_ref_features > 0;
     if (!run) return 7;                                            // no Run launch (the Min_fts rule, as the single call)
@@ -2754,36 +2776,28 @@ static int track_band(const dsdtm_track_desc* d) {
 }
 static const SAVariant kBandVariant[6] = {SA_REG128, SA_REG192, SA_REG256, SA_REG320, SA_REG448, SA_REG704};
 
-extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n_frames, const dsdtm_track_desc* descs,
-                                  dsdtm_track_result* results, dsdtm_track_match* matches, double* residual_norm, uint8_t* in_grid) {
-    if (!ctx) return DSDTM_ERR_INVALID;
-    if (n_frames < 0 || n_frames > DSDTM_TRACK_FRAMES_MAX) { set_err(ctx, "track_frames: n_frames %d outside 0..%d", n_frames, DSDTM_TRACK_FRAMES_MAX); return DSDTM_ERR_INVALID; }
-    if (n_frames == 0) return DSDTM_OK;
-    if (!cam || !descs || !results || !matches || !residual_norm) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
-    const int n = n_frames;
-    const bool resident = descs[0].image == nullptr;               // all or none: frame 0 decides, every other frame must agree
-    // (checked before `results` is touched: in a mixture some results[f].frame are the caller's frames, and stay so)
-    for (int f = 0; f < n; ++f)
-        if ((descs[f].image == nullptr) != resident) {
-            set_err(ctx, "track_frames: frame %d: image is %s, frame 0's is %s (a call runs on resident frames — image NULL, results[f].frame set — for all of its frames or for none)",
-                    f, descs[f].image ? "set" : "NULL", resident ? "NULL" : "set");
-            return DSDTM_ERR_INVALID;
-        }
-    std::vector<dsdtm_frame*> cur;                                 // resident mode: the frames, in the caller's order
-    if (resident) {
-        try { cur.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
-        for (int f = 0; f < n; ++f) cur[(size_t)f] = results[f].frame;
-    }
+struct TrackBatch {
+    int n; bool resident; const dsdtm_camera* cam; const dsdtm_track_desc* descs;
+    std::vector<dsdtm_frame*> cur;           // resident mode: the frames, in the caller's order
+    std::vector<TrackPlan> plans;            // per frame
+    std::vector<ImageRoute> route;           // per frame (image mode)
+    std::vector<int> order;                  // slot -> frame
+    std::vector<int32_t> col0, blk_frame;    // per slot: its first column; per match workgroup: its slot
+    int band_lo[9];                          // slots of band b: [band_lo[b], band_lo[b + 1])
+    size_t MF, C, NZ, NK, NMASK, NB, n_staged, pitch, img, img_pitch, MM;   // MF: feature stride; columns, observations, keyframes, masks, match workgroups, staged images over all frames
+    int max_points;
+    TrackLayout L;
+    uint8_t *h, *g, *hd, *slab;              // the pinned block, the device scratch, the block as the device sees it; image mode: the new frames
+};
+
+// every frame is checked before anything is allocated or enqueued
+static int tracks_check(dsdtm_ctx* ctx, TrackBatch& B) {
+    const int n = B.n;
+    const bool resident = B.resident; const std::vector<dsdtm_frame*>& cur = B.cur;
+    try { B.plans.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+    const dsdtm_track_desc& d0 = B.descs[0];
     for (int f = 0; f < n; ++f) {
-        memset(&results[f], 0, sizeof results[f]);
-        if (resident) results[f].frame = cur[(size_t)f];           // in/out: the caller's before, during and after the call
-    }
-    // ---- every frame is checked before anything is allocated or enqueued ----
-    std::vector<TrackPlan> plans;
-    try { plans.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
-    const dsdtm_track_desc& d0 = descs[0];
-    for (int f = 0; f < n; ++f) {
-        const dsdtm_track_desc* d = &descs[f];
+        const dsdtm_track_desc* d = &B.descs[f];
         const char* field = nullptr;
         if (d->width != d0.width) field = "width";
         else if (d->height != d0.height) field = "height";
@@ -2809,24 +2823,24 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
             }
             if (c == d->ref) { set_err(ctx, "track_frames: frame %d: ref is results[%d].frame itself", f, f); return DSDTM_ERR_INVALID; }
         }
-        if (int rc = track_check_desc(ctx, cam, d, &plans[(size_t)f], resident)) {
+        if (int rc = track_check_desc(ctx, B.cam, d, &B.plans[(size_t)f], resident)) {
             char msg[sizeof ctx->err];
             snprintf(msg, sizeof msg, "%s", ctx->err);
             set_err(ctx, "track_frames: frame %d: %s", f, msg);
             return rc;
         }
         if (d->n_ref_features > 704) { set_err(ctx, "track_frames: frame %d: %d reference features (at most 704)", f, d->n_ref_features); return DSDTM_ERR_INVALID; }
-        if (d->ref->pitch != align_up(plans[(size_t)f].pl.bytes, 256)) { set_err(ctx, "track_frames: frame %d: pyramid pitches differ", f); return DSDTM_ERR_INVALID; }
+        if (d->ref->pitch != align_up(B.plans[(size_t)f].pl.bytes, 256)) { set_err(ctx, "track_frames: frame %d: pyramid pitches differ", f); return DSDTM_ERR_INVALID; }
         if (resident) {
             const dsdtm_frame* c = cur[(size_t)f];
-            const PackedPyr& q = plans[(size_t)f].pl;
+            const PackedPyr& q = B.plans[(size_t)f].pl;
             // (a frame from dsdtm_frame_create with levels or a pitch of its own)
             if (memcmp(c->pl.w, q.w, sizeof(int) * q.levels) || memcmp(c->pl.h, q.h, sizeof(int) * q.levels) || memcmp(c->pl.off, q.off, sizeof(q.off[0]) * q.levels) ||
                 c->pitch != d->ref->pitch) {
                 set_err(ctx, "track_frames: frame %d: levels of results[%d].frame are not those of a %dx%d image with %d levels", f, f, d->width, d->height, d->levels);
                 return DSDTM_ERR_INVALID;
             }
-            if (c->seq > plans[(size_t)f].frames_seq) plans[(size_t)f].frames_seq = c->seq;
+            if (c->seq > B.plans[(size_t)f].frames_seq) B.plans[(size_t)f].frames_seq = c->seq;
         }
     }
     if (resident) {                                                // the same frame twice: named by its later place in the call
@@ -2838,109 +2852,300 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
             if (by_ptr[i].first == by_ptr[i - 1].first && (dup < 0 || by_ptr[i].second < dup)) { dup = by_ptr[i].second; first = by_ptr[i - 1].second; }
         if (dup >= 0) { set_err(ctx, "track_frames: frame %d: results[%d].frame is also frame %d's (a frame at most once per call)", dup, dup, first); return DSDTM_ERR_INVALID; }
     }
-    const TrackPlan& P = plans[0];
-    const PackedPyr& pl = P.pl;
-    const size_t pitch = align_up(pl.bytes, 256), img = (size_t)d0.width * d0.height, MM = (size_t)d0.max_matches;
+    return DSDTM_OK;
+}
 
-    // ---- slot order: by register band (stable) ----
-    std::vector<int> order, slot_of, band;
-    try { order.resize((size_t)n); slot_of.resize((size_t)n); band.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
-    int band_lo[9] = {0};
-    for (int f = 0; f < n; ++f) { band[(size_t)f] = track_band(&descs[f]); band_lo[band[(size_t)f] + 1]++; }
+// slot order: by register band (stable); sizes: columns (each frame padded to whole match workgroups, at least one),
+// observations, keyframes, masks
+static int tracks_order_and_sizes(dsdtm_ctx* ctx, TrackBatch& B) {
+    const int n = B.n;
+    const dsdtm_track_desc& d0 = B.descs[0];
+    B.pitch = align_up(B.plans[0].pl.bytes, 256); B.img = (size_t)d0.width * d0.height; B.MM = (size_t)d0.max_matches;
+    std::vector<int> band;
+    try { B.order.resize((size_t)n); band.resize((size_t)n); B.col0.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+    int* band_lo = B.band_lo;
+    memset(band_lo, 0, sizeof B.band_lo);
+    for (int f = 0; f < n; ++f) { band[(size_t)f] = track_band(&B.descs[f]); band_lo[band[(size_t)f] + 1]++; }
     for (int b = 0; b < 8; ++b) band_lo[b + 1] += band_lo[b];
     {
         int next[8];
         for (int b = 0; b < 8; ++b) next[b] = band_lo[b];
-        for (int f = 0; f < n; ++f) { const int s = next[band[(size_t)f]]++; order[(size_t)s] = f; slot_of[(size_t)f] = s; }
+        for (int f = 0; f < n; ++f) B.order[(size_t)next[band[(size_t)f]]++] = f;
     }
-    // ---- sizes: columns (each frame padded to whole match workgroups, at least one), observations, keyframes, masks ----
-    size_t MF = 1, C = 0, NZ = 0, NK = 0, NMASK = 0;
-    int max_points = 0;
-    std::vector<int32_t> col0, blk_frame;
-    try { col0.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+    B.MF = 1; B.C = B.NZ = B.NK = B.NMASK = 0; B.max_points = 0;
     for (int s = 0; s < n; ++s) {
-        const dsdtm_track_desc* d = &descs[order[(size_t)s]];
-        if ((size_t)d->n_ref_features > MF) MF = (size_t)d->n_ref_features;
-        col0[(size_t)s] = (int32_t)C;
+        const dsdtm_track_desc* d = &B.descs[B.order[(size_t)s]];
+        if ((size_t)d->n_ref_features > B.MF) B.MF = (size_t)d->n_ref_features;
+        B.col0[(size_t)s] = (int32_t)B.C;
         const size_t groups = d->n_points > 0 ? ((size_t)d->n_points + TRACK_COL_GROUP - 1) / TRACK_COL_GROUP : 1;
-        try { for (size_t g = 0; g < groups; ++g) blk_frame.push_back(s); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
-        C += groups * TRACK_COL_GROUP;
-        NZ += (size_t)plans[(size_t)order[(size_t)s]].nnz;
-        NK += (size_t)d->n_kf;
-        if (d->mask) NMASK++;
-        if (d->n_points > max_points) max_points = d->n_points;
+        try { for (size_t g = 0; g < groups; ++g) B.blk_frame.push_back(s); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+        B.C += groups * TRACK_COL_GROUP;
+        B.NZ += (size_t)B.plans[(size_t)B.order[(size_t)s]].nnz;
+        B.NK += (size_t)d->n_kf;
+        if (d->mask) B.NMASK++;
+        if (d->n_points > B.max_points) B.max_points = d->n_points;
     }
-    const size_t NF = (size_t)n, NB = blk_frame.size();
+    B.NB = B.blk_frame.size();
+    return DSDTM_OK;
+}
 
-    // ---- the pinned block (host-mapped) ----
+// the pinned block and the device scratch; how every image travels (which sizes the staging of pageable images); the staging itself
+static int tracks_layout(dsdtm_ctx* ctx, TrackBatch& B) {
+    const size_t NF = (size_t)B.n, MF = B.MF, C = B.C, NZ = B.NZ, NK = B.NK, MM = B.MM;
+    TrackLayout& L = B.L;
+    memset(&L, 0, sizeof L);
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
     // Run's range (slot order, features at stride MF): inputs, then the poses / counts / statistics Run writes
-    const size_t h_run = o;
-    const size_t h_px = take(NF * MF * 8), h_bear = take(NF * MF * 24), h_pw = take(NF * MF * 24), h_ini = take(NF * MF),
-                 h_nf = take(NF * 4), h_tr = take(NF * 96), h_rp = take(NF * sizeof(void*)), h_cp = take(resident ? NF * sizeof(void*) : 0);
-    const size_t h_T = take(NF * 96), h_nt = take(NF * 4), h_st = take(NF * sizeof(dsdtm_align_stats));
-    const size_t run_bytes = o - h_run, run_out_bytes = o - h_T;
+    L.h_run = o;
+    L.h_px = take(NF * MF * 8); L.h_bear = take(NF * MF * 24); L.h_pw = take(NF * MF * 24); L.h_ini = take(NF * MF);
+    L.h_nf = take(NF * 4); L.h_tr = take(NF * 96); L.h_rp = take(NF * sizeof(void*)); L.h_cp = take(B.resident ? NF * sizeof(void*) : 0);
+    L.h_T = take(NF * 96); L.h_nt = take(NF * 4); L.h_st = take(NF * sizeof(dsdtm_align_stats));
+    L.run_bytes = o - L.h_run; L.run_out_bytes = o - L.h_T;
     // the local maps and masks (slot order, columns padded): one range, copied up in one piece
-    const size_t h_map = o;
-    const size_t h_mask = take(NMASK * img), h_fmask = take(NF * sizeof(void*)), h_bf = take(NB * 4), h_c0 = take(NF * 4),
-                 h_np = take(NF * 4), h_mpw = take(C * 24), h_found = take(C * 4), h_bad = take(C), h_off = take((C + 1) * 4),
-                 h_okf = take(NZ * 4), h_opx = take(NZ * 8), h_olv = take(NZ * 4), h_ob = take(NZ * 24), h_Tkf = take(NK * 96),
-                 h_kfp = take(NK * sizeof(void*));
-    const size_t map_bytes = o - h_map;
+    L.h_map = o;
+    L.h_mask = take(B.NMASK * B.img); L.h_fmask = take(NF * sizeof(void*)); L.h_bf = take(B.NB * 4); L.h_c0 = take(NF * 4);
+    L.h_np = take(NF * 4); L.h_mpw = take(C * 24); L.h_found = take(C * 4); L.h_bad = take(C); L.h_off = take((C + 1) * 4);
+    L.h_okf = take(NZ * 4); L.h_opx = take(NZ * 8); L.h_olv = take(NZ * 4); L.h_ob = take(NZ * 24); L.h_Tkf = take(NK * 96);
+    L.h_kfp = take(NK * sizeof(void*));
+    L.map_bytes = o - L.h_map;
     // results the kernels post straight into the pinned block
-    const size_t h_cnt = take(NF * 16), h_match = take(NF * MM * sizeof(dsdtm_track_match)), h_Topt = take(NF * 96),
-                 h_sm = take(NF * sizeof(dsdtm_pose_opt_summary)), h_rn = take(NF * MM * 8), h_grid = take(C);
+    L.h_cnt = take(NF * 16); L.h_match = take(NF * MM * sizeof(dsdtm_track_match)); L.h_Topt = take(NF * 96);
+    L.h_sm = take(NF * sizeof(dsdtm_pose_opt_summary)); L.h_rn = take(NF * MM * 8); L.h_grid = take(C);
     // pageable host images are staged here
-    size_t n_staged = 0;
-    std::vector<uint8_t> kind;   // 0: staged, 1: pinned (host-mapped), 2: device, 3: device through the copy engine, 4: pinned through the copy engine
-    std::vector<const void*> src;
-    try { kind.resize(NF); src.resize(NF); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
-    for (int f = 0; f < n && !resident; ++f) {
-        const dsdtm_track_desc* d = &descs[f];
-        bool pinned_image = false, device_image = false;
-        hipPointerAttribute_t pa_;
-        if (hipPointerGetAttributes(&pa_, d->image) == hipSuccess) {
-            device_image = pa_.type == hipMemoryTypeDevice;
-            pinned_image = pa_.type == hipMemoryTypeHost && d->stride == d->width;
-            if (device_image && pa_.device != ctx->device) { set_err(ctx, "track_frames: frame %d: the image lives on device %d, the context on %d", f, pa_.device, ctx->device); return DSDTM_ERR_INVALID; }
-        } else (void)hipGetLastError();
-        kind[(size_t)f] = 0; src[(size_t)f] = nullptr;
-        if (device_image) {
-            kind[(size_t)f] = (d->stride == d->width && !(((size_t)d->image) & 15)) ? 2 : 3;
-            src[(size_t)f] = d->image;
-        } else if (pinned_image) {
-            void* p_ = nullptr;
-            if (!(((size_t)d->image) & 15) && hipHostGetDevicePointer(&p_, (void*)d->image, 0) == hipSuccess) { kind[(size_t)f] = 1; src[(size_t)f] = p_; }
-            else { (void)hipGetLastError(); kind[(size_t)f] = 4; src[(size_t)f] = d->image; }
-        } else n_staged++;
+    B.n_staged = 0;
+    try { B.route.resize(NF); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+    for (int f = 0; f < B.n && !B.resident; ++f) {
+        const dsdtm_track_desc* d = &B.descs[f];
+        B.route[(size_t)f] = route_image(ctx, d->image, d->width, d->stride, true);
+        if (B.route[(size_t)f].route == OTHER_DEVICE) { set_err(ctx, "track_frames: frame %d: the image lives on device %d, the context on %d", f, B.route[(size_t)f].device, ctx->device); return DSDTM_ERR_INVALID; }
+        if (B.route[(size_t)f].route == STAGED) B.n_staged++;
     }
-    const size_t img_pitch = align_up(img, 256);             // (ingest_kernel reads 16-byte aligned sources)
-    const size_t h_img = take(n_staged * img_pitch);
-    const size_t h_total = o;
-    // ---- device scratch ----
+    B.img_pitch = align_up(B.img, 256);                      // (ingest_kernel reads 16-byte aligned sources)
+    L.h_img = take(B.n_staged * B.img_pitch);
+    L.h_total = o;
     o = 0;
-    const size_t g_run = take(run_bytes), g_map = take(map_bytes), g_pw = take(C * 24), g_cell = take(C * 4), g_px0 = take(C * 16),
-                 g_px = take(C * 16), g_ck = take(C * 4), g_cf = take(C * 4), g_rpx = take(C * 8), g_rl = take(C * 4), g_rb = take(C * 24),
-                 g_ib = take(C), g_sl = take(C * 4), g_cv = take(C), g_grid = take(C), g_pob = take(NF * MM * 24),
-                 g_pow = take(NF * MM * 24), g_pol = take(NF * MM * 4), g_pou = take(NF * MM), g_pon = take(NF * 4), g_Topt = take(NF * 96);
-    const size_t g_total = o;
-    if (int rc = ensure_stage(ctx, h_total > g_total ? h_total : g_total)) return rc;
-    uint8_t* h = (uint8_t*)ctx->h_pinned;
-    uint8_t* g = (uint8_t*)ctx->d_stage;
+    L.g_run = take(L.run_bytes); L.g_map = take(L.map_bytes); L.g_pw = take(C * 24); L.g_cell = take(C * 4); L.g_px0 = take(C * 16);
+    L.g_px = take(C * 16); L.g_ck = take(C * 4); L.g_cf = take(C * 4); L.g_rpx = take(C * 8); L.g_rl = take(C * 4); L.g_rb = take(C * 24);
+    L.g_ib = take(C); L.g_sl = take(C * 4); L.g_cv = take(C); L.g_grid = take(C); L.g_pob = take(NF * MM * 24);
+    L.g_pow = take(NF * MM * 24); L.g_pol = take(NF * MM * 4); L.g_pou = take(NF * MM); L.g_pon = take(NF * 4); L.g_Topt = take(NF * 96);
+    L.g_total = o;
+    if (int rc = ensure_stage(ctx, L.h_total > L.g_total ? L.h_total : L.g_total)) return rc;
+    B.h = (uint8_t*)ctx->h_pinned;
+    B.g = (uint8_t*)ctx->d_stage;
     void* hd_ = nullptr;
     HIP_TRY(ctx, hipHostGetDevicePointer(&hd_, ctx->h_pinned, 0));
-    uint8_t* hd = (uint8_t*)hd_;
-    hipStream_t stream = ctx->stream;
-    uint8_t* const gr = g + g_run - h_run;      // device address of pinned offset X inside Run's range: gr + X
-    uint8_t* const gm = g + g_map - h_map;      // ... inside the map range: gm + X
+    B.hd = (uint8_t*)hd_;
+    return DSDTM_OK;
+}
 
-    // ---- the slab (resident mode: none — the frames are where they are) ----
-    const size_t slab_bytes = pitch * NF;
+// Run's range: features, poses seeded (src/Tracking.cpp:201), counts and statistics cleared
+static void tracks_pack_run(TrackBatch& B) {
+    const TrackLayout& L = B.L;
+    uint8_t* const h = B.h;
+    const size_t NF = (size_t)B.n, MF = B.MF;
+    for (int s = 0; s < B.n; ++s) {
+        const dsdtm_track_desc* d = &B.descs[B.order[(size_t)s]];
+        const size_t nf = (size_t)d->n_ref_features, S = (size_t)s;
+        if (nf) {
+            memcpy(h + L.h_px + S * MF * 8, d->ref_px_xy, nf * 8); memcpy(h + L.h_bear + S * MF * 24, d->ref_bearing, nf * 24);
+            memcpy(h + L.h_pw + S * MF * 24, d->ref_p_world, nf * 24); memcpy(h + L.h_ini + S * MF, d->ref_initial, nf);
+        }
+        ((int32_t*)(h + L.h_nf))[s] = (int32_t)nf;
+        memcpy(h + L.h_tr + S * 96, d->T_ref_w, 96);
+        ((const uint8_t**)(h + L.h_rp))[s] = d->ref->d;
+        if (B.resident) ((const uint8_t**)(h + L.h_cp))[s] = B.cur[(size_t)B.order[S]]->d;
+        memcpy(h + L.h_T + S * 96, d->T_seed, 96);
+    }
+    memset(h + L.h_nt, 0, NF * 4);
+    memset(h + L.h_st, 0, NF * sizeof(dsdtm_align_stats));
+}
+
+// the new frames: level 0 of each into its slot of the slab — the first slot's ingest also moves Run's range (a first slot that
+// travels by the copy engine gets an ingest launch with no image for it) —, then the pyramids. Resident: Run's range only.
+static int tracks_ingest(dsdtm_ctx* ctx, TrackBatch& B, hipStream_t stream) {
+    const TrackLayout& L = B.L;
+    const RunRange run_range = {B.hd + L.h_run, B.g + L.g_run, L.run_bytes};
+    if (B.resident) { HIP_TRY(ctx, ingest_launch(nullptr, nullptr, 0, run_range.src, run_range.dst, run_range.bytes, stream)); return DSDTM_OK; }
+    size_t staged = 0;
+    for (int s = 0; s < B.n; ++s) {
+        const int f = B.order[(size_t)s];
+        const dsdtm_track_desc* d = &B.descs[f];
+        ImageRoute r = B.route[(size_t)f];
+        if (r.route == STAGED) {
+            copy_rows(B.h + L.h_img + staged * B.img_pitch, (size_t)d->width, d->image, (size_t)d->stride, (size_t)d->width, (size_t)d->height);
+            r.dev = B.hd + L.h_img + staged * B.img_pitch;
+            staged++;
+        }
+        if (int rc = enqueue_level0(ctx, r, d->image, d->width, d->height, d->stride, B.slab + (size_t)s * B.pitch, s == 0 ? &run_range : nullptr, stream)) return rc;
+    }
+    const TrackPlan& P = B.plans[0];
+    return dsdtm_pyrdown_batch_device(ctx, B.slab, B.pitch, B.n, P.pl.levels, P.pl.w, P.pl.h, P.st, P.pl.off, stream);
+}
+
+// Run: one launch per register band present, one-CU kernels, reference pyramids through the pointer table
+static int tracks_run_bands(dsdtm_ctx* ctx, TrackBatch& B, hipStream_t stream) {
+    const TrackLayout& L = B.L;
+    const size_t MF = B.MF;
+    uint8_t* const gr = B.g + L.g_run - L.h_run;      // device address of pinned offset X inside Run's range: gr + X
+    for (int b = 0; b < 6; ++b) {
+        const int cnt = B.band_lo[b + 1] - B.band_lo[b];
+        if (cnt <= 0) continue;
+        const size_t S = (size_t)B.band_lo[b];
+        dsdtm_batch_desc bd;
+        memset(&bd, 0, sizeof bd);
+        bd.n_pairs = cnt; bd.max_features = (int)MF;
+        fill_levels(bd, B.plans[0].pl);
+        bd.pyr_pitch = B.pitch;
+        bd.ref_pyr = B.resident ? B.cur[(size_t)B.order[S]]->d : B.slab + S * B.pitch;   // (not read by the pointer-table kernel: a range of the right size)
+        bd.cur_pyr = bd.ref_pyr;                                  // (resident: not read either — every pair goes through cur_ptrs)
+        bd.px_xy = (const float*)(gr + L.h_px) + S * MF * 2; bd.bearing = (const double*)(gr + L.h_bear) + S * MF * 3;
+        bd.p_world = (const double*)(gr + L.h_pw) + S * MF * 3; bd.initial = gr + L.h_ini + S * MF;
+        bd.n_features = (const int32_t*)(gr + L.h_nf) + S;
+        bd.T_ref_w = (const double*)(gr + L.h_tr) + S * 12; bd.T_cur_w = (double*)(gr + L.h_T) + S * 12;
+        bd.n_tracked = (int32_t*)(gr + L.h_nt) + S; bd.stats = (dsdtm_align_stats*)(gr + L.h_st) + S;
+        LaunchMode mode;
+        mode.single = true; mode.one_cu = true; mode.variant = (int)kBandVariant[b];
+        mode.ref_ptrs = (const uint8_t* const*)(gr + L.h_rp) + S;
+        if (B.resident) mode.cur_ptrs = (const uint8_t* const*)(gr + L.h_cp) + S;
+        if (int rc = launch_batch(ctx, &bd, B.cam, &B.descs[0].align, stream, mode, nullptr)) return rc;
+    }
+    return DSDTM_OK;
+}
+
+// the local maps: packed in slot order (observations name keyframes in the concatenated table)
+static void tracks_pack_maps(TrackBatch& B) {
+    const TrackLayout& L = B.L;
+    uint8_t* h = B.h;
+    const uint8_t* gm = B.g + L.g_map - L.h_map;      // device address of pinned offset X inside the map range: gm + X
+    const int n = B.n;
+    size_t z = 0, kb = 0, mk = 0;
+    int32_t* off = (int32_t*)(h + L.h_off);
+    for (int s = 0; s < n; ++s) {
+        const int f = B.order[(size_t)s];
+        const dsdtm_track_desc* d = &B.descs[f];
+        const size_t M = (size_t)d->n_points, c0 = (size_t)B.col0[(size_t)s], nnz = (size_t)B.plans[(size_t)f].nnz;
+        const size_t cols = (s + 1 < n ? (size_t)B.col0[(size_t)s + 1] : B.C) - c0;
+        ((int32_t*)(h + L.h_c0))[s] = (int32_t)c0;
+        ((int32_t*)(h + L.h_np))[s] = (int32_t)M;
+        if (d->mask) {
+            copy_rows(h + L.h_mask + mk * B.img, (size_t)d->width, d->mask, (size_t)d->mask_stride, (size_t)d->width, (size_t)d->height);
+            ((const uint8_t**)(h + L.h_fmask))[s] = gm + L.h_mask + mk * B.img;
+            mk++;
+        } else ((const uint8_t**)(h + L.h_fmask))[s] = nullptr;
+        if (M) { memcpy(h + L.h_mpw + c0 * 24, d->mp_world, M * 24); memcpy(h + L.h_found + c0 * 4, d->mp_found, M * 4); memcpy(h + L.h_bad + c0, d->mp_bad, M); }
+        for (size_t i = 0; i < cols; ++i) off[c0 + i] = (int32_t)(z + (i < M ? (size_t)d->obs_offset[i] : nnz));
+        if (nnz) {
+            for (size_t j = 0; j < nnz; ++j) ((int32_t*)(h + L.h_okf))[z + j] = d->obs_kf[j] + (int32_t)kb;
+            memcpy(h + L.h_opx + z * 8, d->obs_px, nnz * 8); memcpy(h + L.h_olv + z * 4, d->obs_level, nnz * 4); memcpy(h + L.h_ob + z * 24, d->obs_bearing, nnz * 24);
+        }
+        if (d->n_kf > 0) memcpy(h + L.h_Tkf + kb * 96, d->T_kf_w, (size_t)d->n_kf * 96);
+        for (int k = 0; k < d->n_kf; ++k) ((const uint8_t**)(h + L.h_kfp))[kb + (size_t)k] = d->kf[k]->d;
+        z += nnz; kb += (size_t)d->n_kf;
+    }
+    off[B.C] = (int32_t)z;
+    memcpy(h + L.h_bf, B.blk_frame.data(), B.NB * 4);
+}
+
+// the maps go up on a second stream while Run runs; reprojection + FindMatchDirect over all columns; the replays; the
+// refinements; Run's outputs and the grid flags come back; the one wait
+static int tracks_launch_and_wait(dsdtm_ctx* ctx, TrackBatch& B, bool want_grid, hipStream_t stream) {
+    const TrackLayout& L = B.L;
+    uint8_t *h = B.h, *g = B.g;
+    const int n = B.n;
+    if (!ctx->copy_stream[0]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream[0], hipStreamNonBlocking));
+    HIP_TRY(ctx, hipMemcpyAsync(g + L.g_map, h + L.h_map, L.map_bytes, hipMemcpyHostToDevice, ctx->copy_stream[0]));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream[0]));
+    TrackArgs t; WarpKernelArgs wa; A2DKernelArgs aa; PoseOptArgs pa;
+    // (resident: aa.cur_pyr is not read — the workgroups go through t.cur_ptrs)
+    bind_track_kernels(L, g, B.hd, B.cam, &B.descs[0], B.plans[0], n, (int)B.C, (int)B.NK, B.resident ? B.cur[(size_t)B.order[0]]->d : B.slab,
+                       B.pitch, t, wa, aa, pa);
+    const uint8_t *gr = g + L.g_run - L.h_run, *gm = g + L.g_map - L.h_map;
+    t.n_frames = n; t.blk_frame = (const int32_t*)(gm + L.h_bf); t.f_col0 = (const int32_t*)(gm + L.h_c0); t.f_np = (const int32_t*)(gm + L.h_np);
+    t.f_mask = (const uint8_t* const*)(gm + L.h_fmask); t.in_grid = g + L.g_grid; t.max_points = B.max_points;
+    t.cur_ptrs = B.resident ? (const uint8_t* const*)(gr + L.h_cp) : nullptr;
+    t.run_out_n16 = 0;     // (n frames' Run results are too many for the match kernel's posted writes, the single call's way: one copy, below)
+    memset(h + L.h_cnt, 0, (size_t)n * 16); memset(h + L.h_sm, 0, (size_t)n * sizeof(dsdtm_pose_opt_summary));
+    HIP_TRY(ctx, track_match_launch(t, wa, aa, stream));
+    HIP_TRY(ctx, track_replay_launch(t, stream));
+    HIP_TRY(ctx, pose_opt_launch(pa, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h + L.h_T, g + L.g_run + (L.h_T - L.h_run), L.run_out_bytes, hipMemcpyDeviceToHost, stream));
+    if (want_grid) HIP_TRY(ctx, hipMemcpyAsync(h + L.h_grid, g + L.g_grid, B.C, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    frames_settle(ctx);
+    return DSDTM_OK;
+}
+
+// the frames (all or nothing; resident: the caller's own, untouched) and every frame's results, in the caller's order
+static int tracks_frames_and_readback(dsdtm_ctx* ctx, TrackBatch& B, size_t slab_bytes, dsdtm_track_result* results, dsdtm_track_match* matches,
+                                      double* residual_norm, uint8_t* in_grid) {
+    const int n = B.n; const size_t NF = (size_t)n;
+    const bool resident = B.resident;
+    FrameSlab* sl = resident ? nullptr : new (std::nothrow) FrameSlab();
+    std::vector<dsdtm_frame*> fr;
+    std::vector<size_t> grid_start;
+    bool ok = resident || sl != nullptr;
+    if (ok) { try { fr.assign(NF, nullptr); grid_start.assign(NF, 0); } catch (...) { ok = false; } }
+    for (int s = 0; ok && !resident && s < n; ++s) {
+        dsdtm_frame* f = new (std::nothrow) dsdtm_frame();
+        if (!f) { ok = false; break; }
+        f->owner = ctx; f->device = ctx->device; f->d = B.slab + (size_t)s * B.pitch; f->pitch = B.pitch; f->pl = B.plans[0].pl; f->slab = sl;
+        fr[(size_t)s] = f;
+    }
+    if (!ok) {
+        for (dsdtm_frame* f : fr) delete f;
+        delete sl;
+        set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM;
+    }
+    if (sl) { sl->owner = ctx; sl->device = ctx->device; sl->d = B.slab; sl->bytes = slab_bytes; sl->refs.store(n); }
+    size_t grid_at = 0;
+    for (int f = 0; f < n; ++f) { grid_start[(size_t)f] = grid_at; grid_at += (size_t)B.descs[f].n_points; }
+    for (int s = 0; s < n; ++s) {
+        const int f = B.order[(size_t)s];
+        dsdtm_track_result* res = &results[f];
+        if (!resident) res->frame = fr[(size_t)s];
+        (void)read_track_result(B.h, B.L, (size_t)s, B.MM, B.descs[0].min_tracked, res, matches + (size_t)f * B.MM, residual_norm + (size_t)f * B.MM);   // (settled: checked by the caller)
+        if (in_grid && B.descs[f].n_points > 0) memcpy(in_grid + grid_start[(size_t)f], B.h + B.L.h_grid + (size_t)B.col0[(size_t)s], (size_t)B.descs[f].n_points);
+    }
+    return DSDTM_OK;
+}
+
+extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n_frames, const dsdtm_track_desc* descs,
+                                  dsdtm_track_result* results, dsdtm_track_match* matches, double* residual_norm, uint8_t* in_grid) {
+    if (!ctx) return DSDTM_ERR_INVALID;
+    if (n_frames < 0 || n_frames > DSDTM_TRACK_FRAMES_MAX) { set_err(ctx, "track_frames: n_frames %d outside 0..%d", n_frames, DSDTM_TRACK_FRAMES_MAX); return DSDTM_ERR_INVALID; }
+    if (n_frames == 0) return DSDTM_OK;
+    if (!cam || !descs || !results || !matches || !residual_norm) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
+    const int n = n_frames;
+    const bool resident = descs[0].image == nullptr;               // all or none: frame 0 decides, every other frame must agree
+    // (checked before `results` is touched: in a mixture some results[f].frame are the caller's frames, and stay so)
+    for (int f = 0; f < n; ++f)
+        if ((descs[f].image == nullptr) != resident) {
+            set_err(ctx, "track_frames: frame %d: image is %s, frame 0's is %s (a call runs on resident frames — image NULL, results[f].frame set — for all of its frames or for none)",
+                    f, descs[f].image ? "set" : "NULL", resident ? "NULL" : "set");
+            return DSDTM_ERR_INVALID;
+        }
+    TrackBatch B;
+    B.n = n; B.resident = resident; B.cam = cam; B.descs = descs; B.slab = nullptr;
+    if (resident) {
+        try { B.cur.resize((size_t)n); } catch (...) { set_err(ctx, "out of host memory"); return DSDTM_ERR_NOMEM; }
+        for (int f = 0; f < n; ++f) B.cur[(size_t)f] = results[f].frame;
+    }
+    for (int f = 0; f < n; ++f) {
+        memset(&results[f], 0, sizeof results[f]);
+        if (resident) results[f].frame = B.cur[(size_t)f];         // in/out: the caller's before, during and after the call
+    }
+    if (int rc = tracks_check(ctx, B)) return rc;
+    if (int rc = tracks_order_and_sizes(ctx, B)) return rc;
+    if (int rc = tracks_layout(ctx, B)) return rc;
+    hipStream_t stream = ctx->stream;
+    // the slab (resident mode: none — the frames are where they are)
+    const size_t slab_bytes = B.pitch * (size_t)n;
     unsigned long long frames_seq = 0;          // the latest prefetch number among the pooled slab, the current (resident), reference and key frames
-    uint8_t* slab = resident ? nullptr : pool_take(ctx, slab_bytes, &frames_seq);
+    uint8_t*& slab = B.slab;
+    slab = resident ? nullptr : pool_take(ctx, slab_bytes, &frames_seq);
     const unsigned long long slab_seq = frames_seq;   // (a pooled buffer whose prefetch may still be writing it: it goes back with this number)
-    for (int f = 0; f < n; ++f) if (plans[(size_t)f].frames_seq > frames_seq) frames_seq = plans[(size_t)f].frames_seq;
+    for (int f = 0; f < n; ++f) if (B.plans[(size_t)f].frames_seq > frames_seq) frames_seq = B.plans[(size_t)f].frames_seq;
     if (resident) HIP_TRY(ctx, hipSetDevice(ctx->device));
     else if (!slab && (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&slab, slab_bytes) != hipSuccess)) {
         (void)hipGetLastError();
@@ -2953,235 +3158,26 @@ extern "C" int dsdtm_track_frames(dsdtm_ctx* ctx, const dsdtm_camera* cam, int n
         if (slab && !pool_give(ctx, ctx, ctx->device, slab, slab_bytes, slab_seq)) (void)hipFree(slab);
         return rc;
     };
-#define TRACKS_TRY(call)                                                                                       \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
-    } while (0)
-
     if (int rc = frames_consume(ctx, frames_seq, stream)) return fail(rc);
-    // ---- 1. Run's range: features, poses seeded (src/Tracking.cpp:201), counts and statistics cleared ----
-    for (int s = 0; s < n; ++s) {
-        const dsdtm_track_desc* d = &descs[order[(size_t)s]];
-        const size_t nf = (size_t)d->n_ref_features, S = (size_t)s;
-        if (nf) {
-            memcpy(h + h_px + S * MF * 8, d->ref_px_xy, nf * 8);
-            memcpy(h + h_bear + S * MF * 24, d->ref_bearing, nf * 24);
-            memcpy(h + h_pw + S * MF * 24, d->ref_p_world, nf * 24);
-            memcpy(h + h_ini + S * MF, d->ref_initial, nf);
-        }
-        ((int32_t*)(h + h_nf))[s] = (int32_t)nf;
-        memcpy(h + h_tr + S * 96, d->T_ref_w, 96);
-        ((const uint8_t**)(h + h_rp))[s] = d->ref->d;
-        if (resident) ((const uint8_t**)(h + h_cp))[s] = cur[(size_t)order[S]]->d;
-        memcpy(h + h_T + S * 96, d->T_seed, 96);
-    }
-    memset(h + h_nt, 0, NF * 4);
-    memset(h + h_st, 0, NF * sizeof(dsdtm_align_stats));
-    // ---- 2. the new frames: level 0 of each into its slot of the slab (the first ingest also moves Run's range), the pyramids ----
-    if (resident) TRACKS_TRY(ingest_launch(nullptr, nullptr, 0, hd + h_run, g + g_run, run_bytes, stream));   // Run's range only
-    else {
-        size_t staged = 0;
-        bool run_moved = false;
-        for (int s = 0; s < n; ++s) {
-            const int f = order[(size_t)s];
-            const dsdtm_track_desc* d = &descs[f];
-            uint8_t* dst = slab + (size_t)s * pitch;
-            const void* from = src[(size_t)f];
-            const uint8_t k = kind[(size_t)f];
-            if (k == 0) {
-                uint8_t* hs = h + h_img + staged * img_pitch;
-                if (d->stride == d->width) memcpy(hs, d->image, img);
-                else for (int y = 0; y < d->height; ++y) memcpy(hs + (size_t)y * d->width, d->image + (size_t)y * d->stride, (size_t)d->width);
-                from = hd + h_img + staged * img_pitch;
-                staged++;
-            }
-            const void* r_src = run_moved ? nullptr : (const void*)(hd + h_run);
-            void* r_dst = run_moved ? nullptr : (void*)(g + g_run);
-            const size_t r_bytes = run_moved ? 0 : run_bytes;
-            if (k == 3) TRACKS_TRY(hipMemcpy2DAsync(dst, (size_t)d->width, d->image, (size_t)d->stride, (size_t)d->width, (size_t)d->height, hipMemcpyDeviceToDevice, stream));
-            else if (k == 4) TRACKS_TRY(hipMemcpyAsync(dst, d->image, img, hipMemcpyHostToDevice, stream));
-            if (k == 3 || k == 4) { if (!run_moved) TRACKS_TRY(ingest_launch(nullptr, nullptr, 0, r_src, r_dst, r_bytes, stream)); }
-            else TRACKS_TRY(ingest_launch(from, dst, img, r_src, r_dst, r_bytes, stream));
-            run_moved = true;
-        }
-    }
-    if (!resident) { if (int rc = dsdtm_pyrdown_batch_device(ctx, slab, pitch, n, pl.levels, pl.w, pl.h, P.st, pl.off, stream)) return fail(rc); }
-
-    // ---- 3. Run: one launch per register band present, one-CU kernels, reference pyramids through the pointer table ----
+    tracks_pack_run(B);
+    if (int rc = tracks_ingest(ctx, B, stream)) return fail(rc);
     volatile unsigned* h_flag = ctx->h_flags + dsdtm_ctx::FLAG_SINGLE;
     *h_flag = 0;
-    for (int b = 0; b < 6; ++b) {
-        const int lo = band_lo[b], cnt = band_lo[b + 1] - band_lo[b];
-        if (cnt <= 0) continue;
-        const size_t L = (size_t)lo;
-        dsdtm_batch_desc bd;
-        memset(&bd, 0, sizeof bd);
-        bd.n_pairs = cnt; bd.max_features = (int)MF; bd.levels = pl.levels;
-        for (int l = 0; l < pl.levels; ++l) { bd.width[l] = pl.w[l]; bd.height[l] = pl.h[l]; bd.stride[l] = pl.w[l]; bd.level_offset[l] = pl.off[l]; }
-        bd.pyr_pitch = pitch;
-        bd.ref_pyr = resident ? cur[(size_t)order[L]]->d : slab + L * pitch;   // (not read by the pointer-table kernel: a range of the right size)
-        bd.cur_pyr = bd.ref_pyr;                                  // (resident: not read either — every pair goes through cur_ptrs)
-        bd.px_xy = (const float*)(gr + h_px) + L * MF * 2; bd.bearing = (const double*)(gr + h_bear) + L * MF * 3;
-        bd.p_world = (const double*)(gr + h_pw) + L * MF * 3; bd.initial = gr + h_ini + L * MF;
-        bd.n_features = (const int32_t*)(gr + h_nf) + L;
-        bd.T_ref_w = (const double*)(gr + h_tr) + L * 12; bd.T_cur_w = (double*)(gr + h_T) + L * 12;
-        bd.n_tracked = (int32_t*)(gr + h_nt) + L; bd.stats = (dsdtm_align_stats*)(gr + h_st) + L;
-        LaunchMode mode;
-        mode.single = true; mode.one_cu = true; mode.variant = (int)kBandVariant[b];
-        mode.ref_ptrs = (const uint8_t* const*)(gr + h_rp) + L;
-        if (resident) mode.cur_ptrs = (const uint8_t* const*)(gr + h_cp) + L;
-        if (int rc = launch_batch(ctx, &bd, cam, &d0.align, stream, mode, nullptr)) return fail(rc);
-    }
-
-    // ---- 4. the local maps: packed in slot order (observations name keyframes in the concatenated table), copied up on a
-    //         second stream while Run runs ----
-    {
-        size_t cz = 0, z = 0, kb = 0, mk = 0;
-        int32_t* off = (int32_t*)(h + h_off);
-        for (int s = 0; s < n; ++s) {
-            const int f = order[(size_t)s];
-            const dsdtm_track_desc* d = &descs[f];
-            const size_t M = (size_t)d->n_points, c0 = (size_t)col0[(size_t)s], nnz = (size_t)plans[(size_t)f].nnz;
-            const size_t cols = (s + 1 < n ? (size_t)col0[(size_t)s + 1] : C) - c0;
-            ((int32_t*)(h + h_c0))[s] = (int32_t)c0;
-            ((int32_t*)(h + h_np))[s] = (int32_t)M;
-            if (d->mask) {
-                for (int y = 0; y < d->height; ++y) memcpy(h + h_mask + mk * img + (size_t)y * d->width, d->mask + (size_t)y * d->mask_stride, (size_t)d->width);
-                ((const uint8_t**)(h + h_fmask))[s] = gm + h_mask + mk * img;
-                mk++;
-            } else ((const uint8_t**)(h + h_fmask))[s] = nullptr;
-            if (M) {
-                memcpy(h + h_mpw + c0 * 24, d->mp_world, M * 24);
-                memcpy(h + h_found + c0 * 4, d->mp_found, M * 4);
-                memcpy(h + h_bad + c0, d->mp_bad, M);
-            }
-            for (size_t i = 0; i < cols; ++i) off[c0 + i] = (int32_t)(z + (i < M ? (size_t)d->obs_offset[i] : nnz));
-            if (nnz) {
-                for (size_t j = 0; j < nnz; ++j) ((int32_t*)(h + h_okf))[z + j] = d->obs_kf[j] + (int32_t)kb;
-                memcpy(h + h_opx + z * 8, d->obs_px, nnz * 8);
-                memcpy(h + h_olv + z * 4, d->obs_level, nnz * 4);
-                memcpy(h + h_ob + z * 24, d->obs_bearing, nnz * 24);
-            }
-            if (d->n_kf > 0) memcpy(h + h_Tkf + kb * 96, d->T_kf_w, (size_t)d->n_kf * 96);
-            for (int k = 0; k < d->n_kf; ++k) ((const uint8_t**)(h + h_kfp))[kb + (size_t)k] = d->kf[k]->d;
-            cz += cols; z += nnz; kb += (size_t)d->n_kf;
-        }
-        off[C] = (int32_t)z;
-        memcpy(h + h_bf, blk_frame.data(), NB * 4);
-        if (!ctx->copy_stream[0]) TRACKS_TRY(hipStreamCreateWithFlags(&ctx->copy_stream[0], hipStreamNonBlocking));
-        TRACKS_TRY(hipMemcpyAsync(g + g_map, h + h_map, map_bytes, hipMemcpyHostToDevice, ctx->copy_stream[0]));
-        TRACKS_TRY(hipStreamSynchronize(ctx->copy_stream[0]));
-    }
-
-    // ---- 5. reprojection + FindMatchDirect over all columns; the replays; the refinements ----
-    TrackArgs t;
-    memset(&t, 0, sizeof t);
-    t.T_run = (const double*)(gr + h_T); t.n_tracked = (const int32_t*)(gr + h_nt); t.min_tracked = d0.min_tracked;
-    t.run_out_dev = gr + h_T; t.run_out_host = hd + h_T; t.run_out_n16 = 0;     // (Run's results come back by one copy, below)
-    t.T_kf_w = (const double*)(gm + h_Tkf); t.kf_ptrs = (const uint8_t* const*)(gm + h_kfp); t.n_kf = (int)NK;
-    t.mp_world = (const double*)(gm + h_mpw); t.mp_found = (const int32_t*)(gm + h_found); t.mp_bad = gm + h_bad; t.n_points = (int)C;
-    t.obs_offset = (const int32_t*)(gm + h_off); t.obs_kf = (const int32_t*)(gm + h_okf); t.obs_px = (const float*)(gm + h_opx);
-    t.obs_level = (const int32_t*)(gm + h_olv); t.obs_bearing = (const double*)(gm + h_ob);
-    t.mask = nullptr; t.mask_stride = d0.width;
-    t.fx = cam->fx; t.fy = cam->fy; t.cx = cam->cx; t.cy = cam->cy; t.width = cam->width; t.height = cam->height; t.levels = pl.levels;
-    t.cell_size = d0.cell_size; t.grid_cols = P.grid_cols; t.grid_rows = P.grid_rows; t.max_matches = d0.max_matches;
-    track_disc_half_widths(d0.cell_size, t.disc_hw);
-    t.pw = (double*)(g + g_pw); t.cell = (int32_t*)(g + g_cell); t.px0 = (double*)(g + g_px0); t.px = (double*)(g + g_px);
-    t.cand_kf = (int32_t*)(g + g_ck); t.cand_frame = (int32_t*)(g + g_cf); t.ref_px = (float*)(g + g_rpx); t.ref_level = (int32_t*)(g + g_rl);
-    t.ref_bearing = (double*)(g + g_rb); t.init_blocked = g + g_ib; t.search_level = (int32_t*)(g + g_sl); t.converged = g + g_cv;
-    t.matches = (dsdtm_track_match*)(hd + h_match); t.counts = (int32_t*)(hd + h_cnt); t.T_opt = (double*)(g + g_Topt);
-    t.po_bearing = (double*)(g + g_pob); t.po_world = (double*)(g + g_pow); t.po_level = (int32_t*)(g + g_pol); t.po_use = g + g_pou;
-    t.po_n = (int32_t*)(g + g_pon);
-    t.n_frames = n; t.blk_frame = (const int32_t*)(gm + h_bf); t.f_col0 = (const int32_t*)(gm + h_c0); t.f_np = (const int32_t*)(gm + h_np);
-    t.f_mask = (const uint8_t* const*)(gm + h_fmask); t.in_grid = g + g_grid; t.max_points = max_points;
-    t.cur_ptrs = resident ? (const uint8_t* const*)(gr + h_cp) : nullptr;
-
-    WarpKernelArgs wa;
-    memset(&wa, 0, sizeof wa);
-    for (int l = 0; l < pl.levels; ++l) { wa.lv[l].w = pl.w[l]; wa.lv[l].h = pl.h[l]; wa.lv[l].stride = pl.w[l]; wa.lv[l].off = (uint32_t)pl.off[l]; }
-    wa.kf_ptrs = t.kf_ptrs; wa.T_kf_w = t.T_kf_w; wa.T_cur_w_arr = t.T_run; wa.cand_frame = t.cand_frame;
-    wa.cand_kf = t.cand_kf; wa.ref_px = t.ref_px; wa.ref_level = t.ref_level; wa.ref_bearing = t.ref_bearing; wa.p_world = t.pw;
-    wa.search_level = t.search_level; wa.m = (int)C; wa.n_kf = (int)NK; wa.max_search_level = P.max_search_level; wa.levels = pl.levels;
-    wa.n_frames = n; wa.fx = cam->fx; wa.fy = cam->fy; wa.cx = cam->cx; wa.cy = cam->cy; wa.no_xcd = options().fmd_no_xcd;
-    A2DKernelArgs aa;
-    memset(&aa, 0, sizeof aa);
-    aa.cur_pyr = resident ? cur[(size_t)order[0]]->d : slab;      // (resident: not read — the workgroups go through t.cur_ptrs)
-    aa.level = t.search_level; aa.px_xy = t.px; aa.converged = t.converged; aa.m = (int)C; aa.max_iters = d0.align2d_iters;
-    aa.levels = pl.levels; aa.px_level0 = 1; aa.frame = t.cand_frame; aa.n_frames = n; aa.pyr_pitch = pitch;
-    for (int l = 0; l < pl.levels; ++l) aa.lv[l] = wa.lv[l];
-
-    PoseOptArgs pa;
-    pa.n_frames = n; pa.max_features = d0.max_matches; pa.max_iterations = d0.pose_opt.max_iterations;
-    pa.n_features = t.po_n; pa.bearing = t.po_bearing; pa.p_world = t.po_world; pa.level = t.po_level; pa.use = t.po_use;
-    pa.T_cur_w = t.T_opt; pa.T_mirror = (double*)(hd + h_Topt); pa.residual_norm = (double*)(hd + h_rn); pa.summary = (dsdtm_pose_opt_summary*)(hd + h_sm);
-    pa.force_variant = 3;                                          // one wave / four waves per frame by its match count, as the single call
-
-    memset(h + h_cnt, 0, NF * 16); memset(h + h_sm, 0, NF * sizeof(dsdtm_pose_opt_summary));
-    TRACKS_TRY(track_match_launch(t, wa, aa, stream));
-    TRACKS_TRY(track_replay_launch(t, stream));
-    TRACKS_TRY(pose_opt_launch(pa, stream));
-    TRACKS_TRY(hipMemcpyAsync(h + h_T, g + g_run + (h_T - h_run), run_out_bytes, hipMemcpyDeviceToHost, stream));
-    if (in_grid) TRACKS_TRY(hipMemcpyAsync(h + h_grid, g + g_grid, C, hipMemcpyDeviceToHost, stream));
-    TRACKS_TRY(hipStreamSynchronize(stream));
-    frames_settle(ctx);
+    if (int rc = tracks_run_bands(ctx, B, stream)) return fail(rc);
+    tracks_pack_maps(B);
+    if (int rc = tracks_launch_and_wait(ctx, B, in_grid != nullptr, stream)) return fail(rc);
     if (*h_flag) {
         *h_flag = 0;
-        for (int i = 0; i < dsdtm_ctx::MAX_STREAMS; ++i)
-            if (ctx->rings[i].used && ctx->rings[i].stream == ctx->stream)
-                (void)hipMemset(ctx->d_counter + i * dsdtm_ctx::COUNTERS_PER_STREAM, 0, sizeof(unsigned) * dsdtm_ctx::COUNTERS_PER_STREAM);
-        set_err(ctx, "sparse-align kernel: intra-workgroup hand-over timed out");
-        return fail(DSDTM_ERR_HIP);
+        clear_stream_counters(ctx, ctx->stream);
+        set_err(ctx, "sparse-align kernel: intra-workgroup hand-over timed out"); return fail(DSDTM_ERR_HIP);
     }
-    const int32_t* cnt = (const int32_t*)(h + h_cnt);
+    const int32_t* cnt = (const int32_t*)(B.h + B.L.h_cnt);
     for (int s = 0; s < n; ++s) {
-        const bool lost = ((const int32_t*)(h + h_nt))[s] < d0.min_tracked;
-        if (cnt[4 * s + 2] == 2 && !lost) { set_err(ctx, "track_frames: frame %d: the replay of the cell walk did not settle", order[(size_t)s]); return fail(DSDTM_ERR_HIP); }
+        const bool lost = ((const int32_t*)(B.h + B.L.h_nt))[s] < descs[0].min_tracked;
+        if (cnt[4 * s + 2] == 2 && !lost) { set_err(ctx, "track_frames: frame %d: the replay of the cell walk did not settle", B.order[(size_t)s]); return fail(DSDTM_ERR_HIP); }
     }
-#undef TRACKS_TRY
-    // ---- the frames (all or nothing; resident: the caller's own, untouched) ----
-    FrameSlab* sl = resident ? nullptr : new (std::nothrow) FrameSlab();
-    std::vector<dsdtm_frame*> fr;
-    bool ok = resident || sl != nullptr;
-    if (ok) { try { fr.assign(NF, nullptr); } catch (...) { ok = false; } }
-    for (int s = 0; ok && !resident && s < n; ++s) {
-        dsdtm_frame* f = new (std::nothrow) dsdtm_frame();
-        if (!f) { ok = false; break; }
-        f->owner = ctx; f->device = ctx->device; f->d = slab + (size_t)s * pitch; f->pitch = pitch; f->pl = pl; f->slab = sl;
-        fr[(size_t)s] = f;
-    }
-    if (!ok) {
-        for (dsdtm_frame* f : fr) delete f;
-        delete sl;
-        set_err(ctx, "out of host memory");
-        return fail(DSDTM_ERR_NOMEM);
-    }
-    if (sl) { sl->owner = ctx; sl->device = ctx->device; sl->d = slab; sl->bytes = slab_bytes; sl->refs.store(n); }
-    size_t grid_at = 0;
-    std::vector<size_t> grid_start(NF, 0);
-    for (int f = 0; f < n; ++f) { grid_start[(size_t)f] = grid_at; grid_at += (size_t)descs[f].n_points; }
-    for (int s = 0; s < n; ++s) {
-        const int f = order[(size_t)s];
-        const size_t S = (size_t)s;
-        dsdtm_track_result* res = &results[f];
-        if (!resident) res->frame = fr[S];
-        memcpy(res->T_run, h + h_T + S * 96, 96);
-        res->n_tracked = ((const int32_t*)(h + h_nt))[s];
-        memcpy(&res->stats, h + h_st + S * sizeof(dsdtm_align_stats), sizeof res->stats);
-        res->lost = res->n_tracked < d0.min_tracked ? 1 : 0;
-        res->n_in_grid = cnt[4 * s];
-        res->n_matches = res->lost ? 0 : cnt[4 * s + 1];
-        res->replay_full_scan = cnt[4 * s + 2] == 1 ? 1 : 0;
-        if (res->lost) memcpy(res->T_opt, res->T_run, 96);
-        else {
-            memcpy(res->T_opt, h + h_Topt + S * 96, 96);
-            memcpy(&res->summary, h + h_sm + S * sizeof(dsdtm_pose_opt_summary), sizeof res->summary);
-            if (res->n_matches > 0) memcpy(matches + (size_t)f * MM, h + h_match + S * MM * sizeof(dsdtm_track_match), (size_t)res->n_matches * sizeof(dsdtm_track_match));
-            if (res->summary.n_residual_blocks > 0) memcpy(residual_norm + (size_t)f * MM, h + h_rn + S * MM * 8, (size_t)res->summary.n_residual_blocks * 8);
-        }
-        if (in_grid && descs[f].n_points > 0) memcpy(in_grid + grid_start[(size_t)f], h + h_grid + (size_t)col0[S], (size_t)descs[f].n_points);
-    }
-    return DSDTM_OK;
+    const int rc = tracks_frames_and_readback(ctx, B, slab_bytes, results, matches, residual_norm, in_grid);
+    return rc ? fail(rc) : DSDTM_OK;
 }
 
 #ifdef DSDTM_DIAG

@@ -160,6 +160,110 @@ static bool batch_failures() {
     return true;
 }
 
+// every way an image can arrive, in one call (dsdtm_track_frames routes each frame's image on its own): level 0 of every frame must
+// reach its slot of the slab, and Run's range must reach the device exactly once — with the first slot's ingest launch, or with a
+// launch of its own where the first slot travels by the copy engine
+enum Arrival { DEV_STRIDED, PAGEABLE, PAGEABLE_STRIDED, PINNED, PINNED_ODD, DEV };
+struct FrameHead { void* owner; int device; uint8_t* d; };      // the first members of dsdtm_frame (api.cpp asserts their layout)
+static uint8_t pixel(int f, int x, int y) { return (uint8_t)(x * 3 + y * 7 + f * 31 + 1); }
+struct Arrivals {
+    int nf = 0;
+    std::vector<Tracker> t;
+    std::vector<dsdtm_track_desc> d;
+    std::vector<dsdtm_track_result> r;
+    std::vector<dsdtm_track_match> ms;
+    std::vector<double> rn;
+    std::vector<std::vector<uint8_t>> pageable;
+    std::vector<std::pair<void*, bool>> owned;      // (allocation, pinned)
+    bool init(dsdtm_ctx* ctx, const std::vector<Arrival>& how, const std::vector<int>& n) {
+        nf = (int)how.size();
+        t.resize((size_t)nf);
+        pageable.resize((size_t)nf);
+        for (int f = 0; f < nf; ++f) {
+            if (!t[(size_t)f].init(ctx, n[(size_t)f], 20, false)) return false;
+            const Arrival a = how[(size_t)f];
+            const int stride = (a == DEV_STRIDED || a == PAGEABLE_STRIDED) ? W + 16 : W;
+            const size_t bytes = (size_t)stride * H + 16;
+            void* base = nullptr;
+            if (a == DEV_STRIDED || a == DEV) { if (hipMalloc(&base, bytes) != hipSuccess) return false; owned.emplace_back(base, false); }
+            else if (a == PINNED || a == PINNED_ODD) { if (hipHostMalloc(&base, bytes, 0) != hipSuccess) return false; owned.emplace_back(base, true); }
+            else { pageable[(size_t)f].assign(bytes, 0); base = pageable[(size_t)f].data(); }
+            uint8_t* im = (uint8_t*)base + (a == PINNED_ODD ? 4 : 0);
+            memset(base, 0xEE, bytes);
+            for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) im[(size_t)y * stride + x] = pixel(f, x, y);
+            t[(size_t)f].d.image = im; t[(size_t)f].d.stride = stride;
+            d.push_back(t[(size_t)f].d);
+        }
+        r.assign((size_t)nf, dsdtm_track_result{});
+        ms.assign((size_t)nf * 200, dsdtm_track_match{});
+        rn.assign((size_t)nf * 200, 0.0);
+        return true;
+    }
+    int run(dsdtm_ctx* ctx) {
+        const dsdtm_camera cam{60.f, 60.f, 32.f, 24.f, 60.f, W, H};
+        return dsdtm_track_frames(ctx, &cam, nf, d.data(), r.data(), ms.data(), rn.data(), nullptr);
+    }
+    bool none_out() const { for (const auto& x : r) if (x.frame) return false; return true; }
+    bool arrived() const {
+        for (int f = 0; f < nf; ++f) {
+            CHECK(r[(size_t)f].frame != nullptr && r[(size_t)f].n_tracked == t[(size_t)f].n);       // (Run read its range on the device)
+            const uint8_t* l0 = ((const FrameHead*)r[(size_t)f].frame)->d;
+            for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) CHECK(l0[(size_t)y * W + x] == pixel(f, x, y));
+        }
+        return true;
+    }
+    void destroy(dsdtm_ctx* ctx) { for (auto& x : r) { dsdtm_frame_destroy(ctx, x.frame); x.frame = nullptr; } }
+    void release(dsdtm_ctx* ctx) {
+        for (auto& x : t) x.release(ctx);
+        for (auto& o : owned) { if (o.second) (void)hipHostFree(o.first); else (void)hipFree(o.first); }
+    }
+};
+struct CallCounts { long copy2d, copy, ingest; };
+static CallCounts counts_now() { return CallCounts{fake_hip_calls("hipMemcpy2DAsync"), fake_hip_calls("hipMemcpyAsync"), fake_hip_calls("ingest_launch")}; }
+
+static bool batch_image_arrivals() {
+    dsdtm_ctx* ctx = nullptr;
+    CHECK(dsdtm_create(0, &ctx) == DSDTM_OK);
+    // (a) frame 0 has the fewest features: it stays in slot 0 behind the sort by register band, and it travels by the copy engine
+    Arrivals a;
+    CHECK(a.init(ctx, {DEV_STRIDED, PAGEABLE, PAGEABLE_STRIDED, PINNED, PINNED_ODD, DEV}, {40, 150, 300, 600, 150, 60}));
+    CallCounts c0 = counts_now();
+    CHECK(a.run(ctx) == DSDTM_OK && a.arrived());
+    CallCounts c1 = counts_now();
+    // one 2-D copy (frame 0); the pinned image at an odd address, the local maps, Run's outputs; four images through the ingest
+    // kernel and ONE launch more for Run's range, because slot 0 came by the copy engine
+    CHECK(c1.copy2d - c0.copy2d == 1 && c1.copy - c0.copy == 3 && c1.ingest - c0.ingest == 4 + 1);
+    a.destroy(ctx);
+    // (b) two frames, both by the copy engine: no image goes through the ingest kernel, Run's range alone does — once
+    Arrivals b;
+    CHECK(b.init(ctx, {DEV_STRIDED, PINNED_ODD}, {40, 150}));
+    c0 = counts_now();
+    CHECK(b.run(ctx) == DSDTM_OK && b.arrived());
+    c1 = counts_now();
+    CHECK(c1.copy2d - c0.copy2d == 1 && c1.copy - c0.copy == 3 && c1.ingest - c0.ingest == 0 + 1);
+    b.destroy(ctx);
+    b.release(ctx);
+    // every HIP call of (a) fails once: an error, no frame handed out, nothing pending; then the call works and the images arrive
+    // (a pinned image whose device alias cannot be had is no error: it travels by the copy engine)
+    const char* points[] = {"ingest_launch", "pyrdown_launch", "sparse_align_launch", "hipMemcpyAsync", "hipMemcpy2DAsync", "hipStreamSynchronize",
+                            "track_match_launch", "track_replay_launch", "pose_opt_launch", "hipMalloc", "hipHostGetDevicePointer"};
+    for (const char* api : points) {
+        for (long nth = 1; nth <= 6; ++nth) {
+            fake_hip_fail(api, nth);
+            const int rc = a.run(ctx);
+            fake_hip_fail(api, 0);
+            if (rc == DSDTM_OK) { CHECK(a.arrived()); a.destroy(ctx); continue; }    // (fewer than nth calls of this api, or not an error)
+            CHECK(a.none_out() && fake_hip_pending() == 0);
+            CHECK(a.run(ctx) == DSDTM_OK && a.arrived());
+            a.destroy(ctx);
+        }
+    }
+    a.release(ctx);
+    dsdtm_destroy(ctx);
+    CHECK(fake_hip_errors().empty());
+    return true;
+}
+
 // two contexts on two threads, each running batches and destroying their frames (TSan)
 static bool two_contexts_two_threads() {
     bool ok[2] = {false, false};
@@ -185,7 +289,8 @@ static bool two_contexts_two_threads() {
 }
 
 int main(int argc, char** argv) {
-    const std::pair<std::string, bool (*)()> all[] = {{"batch_failures", batch_failures}, {"two_contexts_two_threads", two_contexts_two_threads}};
+    const std::pair<std::string, bool (*)()> all[] = {{"batch_failures", batch_failures}, {"batch_image_arrivals", batch_image_arrivals},
+                                                                {"two_contexts_two_threads", two_contexts_two_threads}};
     int failed = 0;
     for (const auto& sc : all) {
         bool wanted = argc < 2;

@@ -4,6 +4,7 @@
 // per row: the frame's plane receives the RAW 16-bit values of the source as it is WHEN THE COPY RUNS (first half of every
 // float row), which is what the tests are about: a staged source that was overwritten too early shows up in the plane.
 // The faked lift hands back the raw value at the rounded pixel (0 -> -1). Test infrastructure only.
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 
@@ -11,8 +12,8 @@
 #include "fake_rgbd.h"
 #include "kernels.h"
 
-static long g_fail_depth = 0, g_fail_lift = 0, g_depth_launches = 0;
-static float g_inv_scale = 0.0f;
+static std::atomic<long> g_fail_depth{0}, g_fail_lift{0}, g_depth_launches{0};   // (two contexts launch from two threads)
+static std::atomic<float> g_inv_scale{0.0f};
 void fake_rgbd_fail(long depth_nth, long lift_nth) { g_fail_depth = depth_nth; g_fail_lift = lift_nth; }
 long fake_rgbd_depth_launches() { return g_depth_launches; }
 float fake_rgbd_last_inv_scale() { return g_inv_scale; }

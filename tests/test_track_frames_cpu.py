@@ -46,7 +46,7 @@ def test_batch_entry_under_address_and_ub_sanitizers(tmp_path):
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
     lines = [l for l in r.stdout.splitlines() if l.startswith(("ok ", "FAILED "))]
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert lines == ["ok batch_failures", "ok two_contexts_two_threads"], lines
+    assert lines == ["ok batch_failures", "ok batch_image_arrivals", "ok two_contexts_two_threads"], lines
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr
 
 

@@ -126,6 +126,72 @@ def capi_band(nf):
     return next(i for i, hi in enumerate((128, 192, 256, 320, 448, 704)) if nf <= hi)
 
 
+@pytest.mark.parametrize("width,height", [(640, 480), (636, 478)])
+def test_every_way_an_image_can_arrive_in_a_batch(gpu_ctx, width, height):
+    """One image-mode call whose six frames' images arrive on every route of dsdtm_track_frames, in this order: device memory
+    row-strided (the copy engine — this frame has the fewest features, so it stays in slot 0 behind the sort by register band and
+    Run's range gets an ingest launch of its own), pageable, pageable row-strided (both staged), pinned and aligned (read in place),
+    pinned at address + 4 (the copy engine), device memory aligned (read in place). Then a call of two frames, both at odd device
+    addresses. Every frame equals dsdtm_track_frame on the same pageable image, and its pyramid is DeviceFrame.from_image's.
+    636 x 478: the byte count is no multiple of 16, the level widths are 636/318/159/80/40."""
+    import torch
+    from tests.test_frame_prefetch_gpu import pyramid_levels, same_pyramid
+    _set_config()
+    cam, kfs, cur, mps = make_world(31, n_points=500, n_kf=2, width=width, height=height)
+    n = width * height
+    rng = np.random.default_rng(9)
+    images = [np.ascontiguousarray(cur.mvImg_Pyr[0])]
+    for _ in range(5):                                                 # the same scene under a little noise: six different images
+        images.append(np.clip(images[0].astype(np.int16) + rng.integers(-2, 3, images[0].shape), 0, 255).astype(np.uint8))
+    frames = [dict(image=im, levels=5, last=_last_with(kfs[0], cam, nf), T_seed=kfs[0].Get_Pose(), align=ALIGN, min_tracked=20,
+                   keyframes=kfs, map_points=mps) for im, nf in zip(images, (100, 150, 250, 300, 180, 120))]
+    assert capi_band(frames[0]["last"].n_features) == 0 and frames[0]["last"].n_features < min(f["last"].n_features for f in frames[1:])
+    want = [_single(gpu_ctx, cam, f) for f in frames]
+    pyr = []
+    for im in images:
+        df = capi.DeviceFrame.from_image(gpu_ctx, im, 5)
+        pyr.append(pyramid_levels(df, width, height, 5))
+        df.close()
+
+    keep = []
+    def device(im, stride, at=0):
+        t = torch.zeros(height * stride + 64, dtype=torch.uint8, device="cuda")
+        t[at:at + height * stride].reshape(height, stride)[:, :width] = torch.from_numpy(im).cuda()
+        keep.append(t)
+        assert t.data_ptr() % 16 == 0
+        return t.data_ptr() + at, stride
+
+    def pinned(im, at=0):
+        t = torch.empty(n + 64, dtype=torch.uint8).pin_memory()
+        a = t.numpy()[at:at + n].reshape(height, width)
+        a[:] = im
+        keep.append(t)
+        assert a.ctypes.data % 16 == at
+        return a.ctypes.data, width
+
+    def check(call, idx, arrivals):
+        for j, (ptr, stride) in enumerate(arrivals):
+            if ptr is not None:
+                call.descs[j].image, call.descs[j].stride = ptr, stride
+        torch.cuda.synchronize()
+        got = call.run()
+        for j, g in zip(idx, got):
+            _same(g, want[j], f"frame {j}")
+            assert same_pyramid(pyramid_levels(g["frame"], width, height, 5), pyr[j]), f"frame {j}: pyramid"
+            g["frame"].close()
+        return got
+
+    strided = np.zeros((height, width + 7), np.uint8)[:, :width]; strided[:] = images[2]
+    six = [dict(f) for f in frames]
+    six[2]["image"] = strided
+    got = check(tracking.TrackBatchCall(gpu_ctx, cam, six), range(6),
+                [device(images[0], width + 40), (None, None), (None, None), pinned(images[3]), pinned(images[4], 4), device(images[5], width)])
+    assert sum((not g["lost"]) and len(g["matches"]) > 20 for g in got) >= 3
+    check(tracking.TrackBatchCall(gpu_ctx, cam, [dict(frames[1]), dict(frames[4])]), (1, 4), [device(images[1], width, 4), device(images[4], width, 4)])
+    for w in want:
+        w["frame"].close()
+
+
 @pytest.mark.parametrize("name", list(Q.SEARCH_WORLDS))
 def test_search_worlds_in_a_batch_equal_the_restatement(gpu_ctx, name):
     """The quirk worlds (tests/quirk_fixtures.py) as frames of a batch of three: each equals the single call, the sequential
