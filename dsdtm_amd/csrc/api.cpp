@@ -206,25 +206,14 @@ namespace {
 struct OptionKey { const char* key; const char* env; int dsdtm::Options::*field; bool flag; };
 const OptionKey kOptionKeys[] = {
     {"no_team", "DSDTM_NO_TEAM", &dsdtm::Options::no_team, true},
-    {"team_min", "DSDTM_TEAM_MIN", &dsdtm::Options::team_min, false},
-    {"team_spread_min", "DSDTM_TEAM_SPREAD_MIN", &dsdtm::Options::team_spread_min, false},
-    {"ws_from", "DSDTM_WS_FROM", &dsdtm::Options::ws_from, false},
-    {"ws_no_windows", "DSDTM_WS_NO_WINDOWS", &dsdtm::Options::ws_no_windows, true},
     {"ws_no_duo", "DSDTM_WS_NO_DUO", &dsdtm::Options::ws_no_duo, true},
     {"ws_no_sort", "DSDTM_WS_NO_SORT", &dsdtm::Options::ws_no_sort, true},
     {"fmd_split", "DSDTM_FMD_SPLIT", &dsdtm::Options::fmd_split, true},
     {"fmd_no_xcd", "DSDTM_FMD_NO_XCD", &dsdtm::Options::fmd_no_xcd, true},
-    {"match_group", "DSDTM_MATCH_GROUP", &dsdtm::Options::match_group, false},
     {"pyr_fused", "DSDTM_PYR_FUSED", &dsdtm::Options::pyr_fused, false},
     {"pyr_band", "DSDTM_PYR_BAND", &dsdtm::Options::pyr_band, false},
-    {"no_zero_copy", "DSDTM_NO_ZERO_COPY", &dsdtm::Options::no_zero_copy, true},
-    {"po_no_cache", "DSDTM_PO_NO_CACHE", &dsdtm::Options::po_no_cache, true},
-    {"a2d_tree", "DSDTM_A2D_TREE", &dsdtm::Options::a2d_tree, true},
     {"no_recover", "DSDTM_NO_RECOVER", &dsdtm::Options::no_recover, true},
     {"team_no_wrap_clear", "DSDTM_TEAM_NO_WRAP_CLEAR", &dsdtm::Options::team_no_wrap_clear, true},
-    {"warp_group", "DSDTM_WARP_GROUP", &dsdtm::Options::warp_group, false},
-    {"po_rows", "DSDTM_PO_ROWS", &dsdtm::Options::po_rows, false},
-    {"a2d_group", "DSDTM_A2D_GROUP", &dsdtm::Options::a2d_group, false},
 };
 std::once_flag g_options_once;
 void options_from_env() {
@@ -1148,8 +1137,7 @@ static int sparse_align_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
     memcpy(h + o_tc, T_cur_w, 96);
     // Resident frames: the kernel reads features and poses straight from the pinned staging block (once per
     // pair, ~17 KB over PCIe) and writes its few results there: no H2D / D2H copy operations around the launch.
-    const bool zero_copy_enabled = !options().no_zero_copy;
-    const bool zero_copy = zero_copy_enabled && !staged_pyr;
+    const bool zero_copy = !staged_pyr;
     if (zero_copy) {
         void* hd = nullptr;
         HIP_TRY(ctx, hipHostGetDevicePointer(&hd, ctx->h_pinned, 0));
@@ -1998,10 +1986,8 @@ extern "C" int dsdtm_match_candidates_frames(dsdtm_ctx* ctx, const dsdtm_frame* 
     const size_t o_rl = o; o += align_up(M * 4, 256);
     const size_t o_rp = o; o += align_up(M * 8, 256);
     const size_t o_px = o; o += align_up(M * 16, 256);          // in and out
-    const size_t in_bytes = o;
     const size_t o_sl = o; o += align_up(M * 4, 256);
     const size_t o_cv = o; o += align_up(M, 256);
-    const size_t out_end = o;
     const size_t o_af = o; o += align_up(M * 32, 256);          // device only
     const size_t o_pb = o; o += align_up(M * 100, 256);
     const size_t o_pp = o; o += align_up(M * 64, 256);
@@ -2021,15 +2007,9 @@ extern "C" int dsdtm_match_candidates_frames(dsdtm_ctx* ctx, const dsdtm_frame* 
     // Every input is read once per candidate and every result written once: the two kernels take them straight
     // from / to the pinned block (no copy operations around the launches); only the warped patches, which the
     // second kernel re-reads at every iteration, live in device memory.
-    const bool zero_copy = !options().no_zero_copy;
-    uint8_t* io = d;
-    if (zero_copy) {
-        void* hd = nullptr;
-        HIP_TRY(ctx, hipHostGetDevicePointer(&hd, ctx->h_pinned, 0));
-        io = (uint8_t*)hd;
-    } else {
-        HIP_TRY(ctx, hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
+    void* hd = nullptr;
+    HIP_TRY(ctx, hipHostGetDevicePointer(&hd, ctx->h_pinned, 0));
+    uint8_t* const io = (uint8_t*)hd;
     WarpKernelArgs a;
     memset(&a, 0, sizeof a);
     a.kf_ptrs = (const uint8_t* const*)(io + o_ptr); a.T_kf_w = (const double*)(io + o_tk);
@@ -2057,7 +2037,6 @@ extern "C" int dsdtm_match_candidates_frames(dsdtm_ctx* ctx, const dsdtm_frame* 
         a.affine = nullptr; a.no_xcd = options().fmd_no_xcd;                    // (nobody reads it here)
         HIP_TRY(ctx, match_launch(a, b, ctx->stream));
     }
-    if (!zero_copy) HIP_TRY(ctx, hipMemcpyAsync(h + o_px, d + o_px, out_end - o_px, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     frames_settle(ctx);
     memcpy(px_xy, h + o_px, M * 16);
@@ -2185,10 +2164,9 @@ extern "C" int dsdtm_pose_optimization(dsdtm_ctx* ctx, const double* bearing, co
     }
     // Up to 512 features the kernel keeps a lane's features in registers (pose_opt.hip, CACHED): every input is read once,
     // so it reads them straight from the pinned block and writes pose, summary and norms there — no copy operations
-    // around the launch (DSDTM_NO_ZERO_COPY=1 restores them). Larger frames re-read their columns at every evaluation
+    // around the launch. Larger frames re-read their columns at every evaluation
     // and are copied to the device first.
-    const bool zero_copy_enabled = !options().no_zero_copy;
-    const bool zero_copy = zero_copy_enabled && n_features > 64 && n_features <= 512 && !options().po_no_cache;
+    const bool zero_copy = n_features > 64 && n_features <= 512;
     if (zero_copy) {
         void* hd = nullptr;
         HIP_TRY(ctx, hipHostGetDevicePointer(&hd, ctx->h_pinned, 0));

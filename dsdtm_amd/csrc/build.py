@@ -6,12 +6,12 @@
     ... [--force] [--define X=1 ...] [--flag F ...]   (extra flags: experiments, see below)
 
 RELEASE (default): exports exactly the symbols include/dsdtm_amd.h declares (linker version script exports.map), reads no
-environment variable, has no dsdtm_debug_* entry, and does not contain the kernels only a diagnostic switch selects
-(align2d_kernel<true>, the 8-per-wave Align2D, warp groups of 8/32/64, match groups of 32/64, the stamps instantiation of the
-register kernel, selftest.hip, the two-kernel FindMatchDirect path). bench.py, __graft_entry__.smoke() and every parity test
-load this one. DIAG (-DDSDTM_DIAG): the same sources with the switches of kernels.h as process-wide variables
-(DSDTM_* environment, dsdtm_debug_set_option), the dsdtm_debug_* entries and those kernels; loaded by tools/ and by the tests
-marked `diag` (fault injection: a team member that stays away, the epoch wrap, A/B of superseded paths).
+environment variable, has no dsdtm_debug_* entry, and does not contain what only the diagnostic build reaches (the stamps
+instantiation of the register kernel, selftest.hip, the two-kernel FindMatchDirect path). bench.py, __graft_entry__.smoke()
+and every parity test load this one. DIAG (-DDSDTM_DIAG): the same sources with the switches of kernels.h as process-wide
+variables (DSDTM_* environment, dsdtm_debug_set_option), the dsdtm_debug_* entries and those kernels; loaded by tools/ and
+by the tests marked `diag` (fault injection: a team member that stays away, the epoch wrap, the fused kernels held to the
+paths they replaced).
 
 Every source is compiled to its own object under csrc/build/ (only when it or a header is newer; in parallel; objects are
 keyed by the flag set), then linked: a change to one kernel file recompiles that file only. The flag set a library was

@@ -47,32 +47,22 @@ struct SAKernelArgs {
     const uint8_t* const* cur_ptrs;
 };
 
-// Diagnostic switches (A/B runs, tests). They exist as VARIABLES only in the diagnostic build (build.py --diag,
-// -DDSDTM_DIAG: libdsdtm_amd_diag.so), where they are process-wide, read from the environment once — by the first
-// dsdtm_create — and changed afterwards through dsdtm_debug_set_option. In the RELEASE build (libdsdtm_amd.so, the
-// library bench.py, smoke() and the parity tests load) they are the compile-time constants below: nothing reads the
-// environment, nothing can change them, and the kernels only they select are not compiled in.
+// Diagnostic switches: the ones a test, a sanitizer scenario or a kernel argument still needs (the A/B switches that rounds
+// 2-6 settled are gone, with the kernels only they selected; profiles/ keeps the measurements). They exist as VARIABLES only
+// in the diagnostic build (build.py --diag, -DDSDTM_DIAG: libdsdtm_amd_diag.so), where they are process-wide, read from the
+// environment once — by the first dsdtm_create — and changed afterwards through dsdtm_debug_set_option. In the RELEASE build
+// (libdsdtm_amd.so, the library bench.py, smoke() and the parity tests load) they are the compile-time constants below:
+// nothing reads the environment, nothing can change them, and the code only they select is not compiled in.
 struct Options {
     int no_team = 0;           // DSDTM_NO_TEAM: large single pairs take the one-CU kernels instead of a team
-    int team_min = 449;        // DSDTM_TEAM_MIN: feature count from which few large pairs run as teams
-    int team_spread_min = 33;  // DSDTM_TEAM_SPREAD_MIN: team size from which members are spread over all XCDs
-    int ws_from = 704;         // DSDTM_WS_FROM: feature counts above this run the workspace kernel in batches
-    int ws_no_windows = 0;     // DSDTM_WS_NO_WINDOWS
-    int match_group = 0;       // DSDTM_MATCH_GROUP: candidates per workgroup of the fused FindMatchDirect kernel (0 = 16; 32 and 64 measured slower)
     int fmd_no_xcd = 0;        // DSDTM_FMD_NO_XCD: the fused FindMatchDirect kernel with plain block numbering (A/B)
-    int fmd_split = 0;         // DSDTM_FMD_SPLIT: FindMatchDirect as two kernels with the patches through HBM (rounds 1-4; A/B)
+    int fmd_split = 0;         // DSDTM_FMD_SPLIT: FindMatchDirect as two kernels with the patches through HBM (rounds 1-4; tests hold it to the fused one)
     int ws_no_sort = 0;        // DSDTM_WS_NO_SORT: the workspace kernels walk a pair's features in list order (A/B, tests)
     int ws_no_duo = 0;         // DSDTM_WS_NO_DUO: 1025..2048 patches on one compute unit (HBM workspace) instead of two
     int pyr_fused = 1;         // DSDTM_PYR_FUSED: 0 never / 1 up to 32 images / 2 whenever the shape allows
     int pyr_band = 0;          // DSDTM_PYR_BAND: rows of the coarsest level per workgroup of the fused kernel (0: auto)
-    int no_zero_copy = 0;      // DSDTM_NO_ZERO_COPY: single-call entry points copy instead of mapping the pinned block
-    int po_no_cache = 0;       // DSDTM_PO_NO_CACHE: pose refinement without features in registers
-    int a2d_tree = 0;          // DSDTM_A2D_TREE: Align2D with DPP tree sums (cost comparison only; not bit-identical)
-    int a2d_group = 4;         // DSDTM_A2D_GROUP: Align2D features per wavefront (4; 8 = diagnostic: 114 VGPRs, measured 7 % slower)
-    int warp_group = 0;        // DSDTM_WARP_GROUP: candidates per workgroup of the warp prelude (2, 8, 16, 32, 64; 0: by batch size)
     int team_no_wrap_clear = 0;  // DSDTM_TEAM_NO_WRAP_CLEAR: the team ring is NOT re-zeroed when the tag epoch wraps (A/B of that hazard only)
     int no_recover = 0;        // DSDTM_NO_RECOVER: a multi-CU launch that timed out is reported, not re-run (tests)
-    int po_rows = 1;           // DSDTM_PO_ROWS: batched pose refinement with four frames per wavefront (0: one frame per wavefront, rounds 1-5; A/B)
 };
 #ifdef DSDTM_DIAG
 Options& options();
@@ -147,7 +137,7 @@ hipError_t pyrdown_fused_launch(uint8_t* pyr, size_t pyr_pitch, int n_images, in
 // host-mapped pinned memory -> device by a kernel (a frame's level 0 + one small second range; see pyrdown.hip)
 hipError_t ingest_launch(const void* src, void* dst, size_t bytes, const void* src2, void* dst2, size_t bytes2, hipStream_t stream);
 
-// Warp prelude: groups of 2 / 64 candidates per 128-thread workgroup (lane = candidate for the FP64 chain, thread = sample for the patches).
+// Warp prelude: groups of 2 / 16 candidates per 128-thread workgroup (lane = candidate for the FP64 chain, thread = sample for the patches).
 struct WarpKernelArgs {
     const uint8_t* kf_pyr;        // n_kf packed pyramids, pitch kf_pitch ...
     const uint8_t* const* kf_ptrs; // ... or (non-null) n_kf base pointers of separately allocated pyramids (device array)

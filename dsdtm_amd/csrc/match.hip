@@ -24,9 +24,9 @@ namespace dsdtm {
 
 // CH = candidates per workgroup (a multiple of MATCH_G, at most 64): phase 1 runs once for all of them — CH lanes of the first
 // wavefront, one FP64 chain each — then phases 2 and 3 go through them MATCH_G at a time (match_body.h). Measured
-// (tools/fmd_bench.py, 51 200 candidates / one frame's 816): CH = 16: 62.4 / 17.2 us; 32: 65.3 / 26.2 us; 64: 70.7 / 43.4 us (the
+// (round 5, profiles/r05_secondary.txt; 51 200 candidates / one frame's 816): CH = 16: 62.4 / 17.2 us; 32: 65.3 / 26.2 us; 64: 70.7 / 43.4 us (the
 // two-kernel path: 64.8 / 18.2 us) — the rounds, not the chain, are what a workgroup spends its time on, and amortising the chain
-// only serialises them. CH = 16 is the product shape; the others stay behind DSDTM_MATCH_GROUP for the record.
+// only serialises them. CH = 16 is the only shape launched.
 template <int CH>
 __global__ __launch_bounds__(256) void match_kernel(const WarpKernelArgs a, const A2DKernelArgs b) {
     static_assert(CH % MATCH_G == 0 && CH <= 64, "candidates per workgroup");
@@ -52,16 +52,8 @@ __global__ __launch_bounds__(256) void match_kernel(const WarpKernelArgs a, cons
 
 hipError_t match_launch(const WarpKernelArgs& wa, const A2DKernelArgs& aa, hipStream_t stream) {
     if (wa.m <= 0) return hipSuccess;
-    const int ch = options().match_group ? options().match_group : 16;
-    const dim3 grid((unsigned)((wa.m + ch - 1) / ch));
-    switch (ch) {
-        case 16: hipLaunchKernelGGL(match_kernel<16>, grid, dim3(256), 0, stream, wa, aa); break;
-#ifdef DSDTM_DIAG                                     // 32 and 64 candidates per group: measured slower, kept for A/B only
-        case 32: hipLaunchKernelGGL(match_kernel<32>, grid, dim3(256), 0, stream, wa, aa); break;
-        case 64: hipLaunchKernelGGL(match_kernel<64>, grid, dim3(256), 0, stream, wa, aa); break;
-#endif
-        default: return hipErrorInvalidValue;
-    }
+    constexpr int CH = 16;
+    hipLaunchKernelGGL(match_kernel<CH>, dim3((unsigned)((wa.m + CH - 1) / CH)), dim3(256), 0, stream, wa, aa);
     return hipGetLastError();
 }
 

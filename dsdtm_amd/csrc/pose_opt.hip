@@ -542,8 +542,7 @@ hipError_t pose_opt_launch(const PoseOptArgs& args, hipStream_t stream) {
     }
     // a few frames (the live tracker refines one): latency counts, four waves share a frame's features;
     // batches: one wave per frame, the solver part is not repeated
-    const bool no_cache = options().po_no_cache != 0;                          // diagnostic (A/B)
-    if (args.force_variant == 4 || (args.force_variant == 0 && args.n_frames > 32 && options().po_rows)) {
+    if (args.force_variant == 4 || (args.force_variant == 0 && args.n_frames > 32)) {
         // batches: four frames per wavefront (round 6: the solver part of an iteration, two thirds of its instructions, runs for
         // four frames at once)
         // — as many frames per wave as still leave every wave slot of the GPU (256 CUs x 4 SIMDs x 2 waves) a wave: a wave's
@@ -557,9 +556,9 @@ hipError_t pose_opt_launch(const PoseOptArgs& args, hipStream_t stream) {
     }
     if (args.force_variant == 1) { hipLaunchKernelGGL((pose_opt_kernel<1, 0>), dim3((unsigned)args.n_frames), dim3(64), 0, stream, args); return hipGetLastError(); }
     if (args.force_variant == 2) { hipLaunchKernelGGL((pose_opt_kernel<4, 1>), dim3((unsigned)args.n_frames), dim3(256), 0, stream, args); return hipGetLastError(); }
-    if (args.n_frames <= 32 && args.max_features > 64 && args.max_features <= 256 && !no_cache)
+    if (args.n_frames <= 32 && args.max_features > 64 && args.max_features <= 256)
         hipLaunchKernelGGL((pose_opt_kernel<4, 1>), dim3((unsigned)args.n_frames), dim3(256), 0, stream, args);
-    else if (args.n_frames <= 32 && args.max_features > 256 && args.max_features <= 512 && !no_cache)
+    else if (args.n_frames <= 32 && args.max_features > 256 && args.max_features <= 512)
         hipLaunchKernelGGL((pose_opt_kernel<4, 2>), dim3((unsigned)args.n_frames), dim3(256), 0, stream, args);
     else if (args.n_frames <= 32 && args.max_features > 64)
         hipLaunchKernelGGL((pose_opt_kernel<4, 0>), dim3((unsigned)args.n_frames), dim3(256), 0, stream, args);

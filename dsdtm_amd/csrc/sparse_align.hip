@@ -2099,13 +2099,15 @@ constexpr int TEAM_NPW = 4;
 static int team_pairs_pad(int n_pairs, int k) {
     // members of a team are workgroups b, b + P, b + 2P ..: P a multiple of 8 keeps a team on one XCD (one L2, 32
     // CUs); teams of more than 32 members cannot fit one XCD and are spread over all of them instead (P odd)
-    if (k < options().team_spread_min) return (n_pairs + 7) / 8 * 8;
+    constexpr int TEAM_SPREAD_MIN = 33;
+    if (k < TEAM_SPREAD_MIN) return (n_pairs + 7) / 8 * 8;
     return n_pairs | 1;
 }
 int sparse_align_team_size(int n_pairs, int max_features, int num_cus) {
     // from 449 features a team of 2..3 CUs beats the 11 + 1 wave register kernel on one CU (N = 600: 0.113 vs
     // 0.121 ms per Run); below, one CU wins (N = 300: 0.108 vs 0.115 ms).
-    if (max_features < options().team_min || n_pairs <= 0) return 0;
+    constexpr int TEAM_MIN = 449;
+    if (max_features < TEAM_MIN || n_pairs <= 0) return 0;
     const int k = (max_features + TEAM_NPW * 64 - 1) / (TEAM_NPW * 64);
     // every member must be resident at once (they spin on each other): the LIVE workgroups (n_pairs * k; the
     // padding workgroups exit at once) may take half the CUs
@@ -2140,19 +2142,19 @@ hipError_t sparse_align_launch_team(const SAKernelArgs& args, int k, hipStream_t
 //   <= 128 features: 2+1 waves x 4 slots     <= 192: 3+1 x 3     <= 256: 4+1 x 2
 //   <= 320 features: 5+1 x 2 (BASELINE shape) <= 448: 7+1 x 1     <= 704: 11+1 x 1
 SAVariant sparse_align_pick_variant(int max_features) {
-    if (max_features > options().ws_from) return SA_WS;   // 704 unless a diagnostic run moved it
+    constexpr int WS_FROM = 704;   // feature counts above this run the workspace kernel in batches
+    if (max_features > WS_FROM) return SA_WS;
     if (max_features <= 128) return SA_REG128;
     if (max_features <= 192) return SA_REG192;
     if (max_features <= 256) return SA_REG256;
     if (max_features <= 320) return SA_REG320;
     if (max_features <= 448) return SA_REG448;
-    if (max_features <= 704) return SA_REG704;
-    return SA_WS;
+    return SA_REG704;
 }
 
 size_t sparse_align_workspace_bytes(int n_pairs, int max_features) {
     if (sparse_align_pick_variant(max_features) != SA_WS) return 0;
-    if (!options().ws_no_windows && (max_features + 63) / 64 * 64 <= 1024) return 0;     // parked in LDS
+    if ((max_features + 63) / 64 * 64 <= 1024) return 0;     // parked in LDS
     // (1025..2048 patches: the two-member kernel needs DUO_BYTES per pair, less than the parking space reserved here)
     return (size_t)n_pairs * ws_doubles_per_pair(max_features) * sizeof(double);
 }
@@ -2216,7 +2218,7 @@ bool sparse_align_uses_duo(int max_features, bool have_workspace) {
     const int npad = (max_features + 63) / 64 * 64;
     // (only where two halves cost no more lane rounds than the whole: 2000 patches = 2 x 2 rounds of 512 lanes
     // against 4; 1500 patches would be 2 x 2 against 3 — measured 10 % slower on two compute units)
-    return !options().ws_no_windows && npad > 1024 && npad <= 2048 && !options().ws_no_duo && have_workspace &&
+    return npad > 1024 && npad <= 2048 && !options().ws_no_duo && have_workspace &&
            2 * (((npad / 64 + 1) / 2 * 64 + WS_THREADS - 1) / WS_THREADS) <= (npad + WS_THREADS - 1) / WS_THREADS;
 }
 
@@ -2232,9 +2234,8 @@ hipError_t sparse_align_launch(const SAKernelArgs& args, SAVariant variant, int 
         case SA_WS: {
             if (args.ref_ptrs) return hipErrorInvalidValue;              // (register kernels only: <= 704 features)
             const int npad = (args.max_features + 63) / 64 * 64;
-            const bool ws_windows = !options().ws_no_windows;
             const dim3 grid((unsigned)args.n_pairs);
-            if (ws_windows && npad <= 1024) {
+            if (npad <= 1024) {
                 // everything a pass needs in LDS: window origins + windows + parked grid inputs (4 + 60 + 88 KB)
                 constexpr size_t lds = (16 + WS_DWORDS) * 1024 * sizeof(uint32_t);
                 const hipError_t attr = optin_dynamic_lds<sparse_align_ws_kernel<WS_NPW, 1024, true>>(lds);
@@ -2249,7 +2250,7 @@ hipError_t sparse_align_launch(const SAKernelArgs& args, SAVariant variant, int 
                 if (ez != hipSuccess) return ez;
                 const dim3 grid2((unsigned)((args.n_pairs + 7) / 8 * 16));
                 hipLaunchKernelGGL((sparse_align_ws_kernel<WS_NPW, 1024, true, 2>), grid2, dim3(WS_THREADS), lds, stream, args);
-            } else if (ws_windows && npad <= 2048) {
+            } else if (npad <= 2048) {
                 const hipError_t attr = optin_dynamic_lds<sparse_align_ws_kernel<WS_NPW, 2048>>(16 * 2048 * sizeof(uint32_t));
                 if (attr != hipSuccess) return attr;
                 hipLaunchKernelGGL((sparse_align_ws_kernel<WS_NPW, 2048>), grid, dim3(WS_THREADS), 16 * 2048 * sizeof(uint32_t), stream, args);

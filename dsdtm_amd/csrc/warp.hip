@@ -3,7 +3,7 @@
 // Replaces reference src/Feature_alignment.cpp:160-190 (SolveAffineMatrix), :192-204
 // (GetBestSearchLevel), :206-259 (WarpAffine), :261-275 (GetPatchNoBoarder), including the
 // integer-division quirk W1 (`1/(1<<lvl)` is 0 for lvl>=1, :231) and the float->u8 truncation.
-// Groups of 2 or 64 candidates per 128-thread workgroup: the 2x2 affine is evaluated in FP64 ONCE per candidate
+// Groups of 2 or 16 candidates per 128-thread workgroup: the 2x2 affine is evaluated in FP64 ONCE per candidate
 // (lane = candidate), then the group's 10x10 bordered patches are sampled thread = sample (warp_kernel below).
 //
 // The outputs are BYTES (float sample positions truncated to u8) and a search level decided by a
@@ -24,7 +24,7 @@
 
 namespace dsdtm {
 
-// G candidates per 128-thread group (2 for one frame's search, 64 for batches), two phases:
+// G candidates per 128-thread group (2 for one frame's search, 16 for batches), two phases:
 //  1. lane = candidate (G of the 128 lanes): the FP64 chain — SolveAffineMatrix, GetBestSearchLevel, the inverse affine —
 //     ONCE per candidate. (Round 1-3: one group per candidate with all 128 lanes evaluating the same chain: 2 waves x ~2 k
 //     dependent FP64 instructions per candidate, 96 % of the kernel; 51 200 candidates took 213 us.)
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(128) void warp_kernel(const WarpKernelArgs a) {
     // 2 x UNROLL loads in flight instead of 2 (64 candidates per group: 50 dependent round trips per thread -> 10).
     warp_samples<128>(s_c, ng, tid, s_pb, s_pp);
     __syncthreads();
-    // (c0 * 100 and c0 * 64 are multiples of 4 for every G used — 2 and 64 — and the scratch sections are 256-byte aligned)
+    // (c0 * 100 and c0 * 64 are multiples of 4 for every G used — 2 and 16 — and the scratch sections are 256-byte aligned)
     {
         uint32_t* __restrict__ dst = (uint32_t*)(a.patch_border + (size_t)c0 * 100);
         const uint32_t* src = (const uint32_t*)s_pb;
@@ -67,19 +67,9 @@ hipError_t warp_launch(const WarpKernelArgs& args, hipStream_t stream) {
     if (args.m <= 0) return hipSuccess;
     // few candidates (one frame's search: ~800): groups of 2 — the call is bound by the latency of one candidate's FP64
     // chain, so the sampling loop behind it is kept to two rounds and the groups spread over every compute unit;
-    // batches: groups of 64 (one full wave of phase-1 lanes)
-    const int g = options().warp_group ? options().warp_group : (args.m < 8192 ? 2 : 16);
-    const dim3 grid((unsigned)((args.m + g - 1) / g));
-    switch (g) {
-        case 2: hipLaunchKernelGGL(warp_kernel<2>, grid, dim3(128), 0, stream, args); break;
-        case 16: hipLaunchKernelGGL(warp_kernel<16>, grid, dim3(128), 0, stream, args); break;
-#ifdef DSDTM_DIAG                                     // group sizes that were measured and not kept (A/B)
-        case 8: hipLaunchKernelGGL(warp_kernel<8>, grid, dim3(128), 0, stream, args); break;
-        case 32: hipLaunchKernelGGL(warp_kernel<32>, grid, dim3(128), 0, stream, args); break;
-        case 64: hipLaunchKernelGGL(warp_kernel<64>, grid, dim3(128), 0, stream, args); break;
-#endif
-        default: return hipErrorInvalidValue;
-    }
+    // batches: groups of 16 (8, 32 and 64 were measured and not kept)
+    if (args.m < 8192) hipLaunchKernelGGL(warp_kernel<2>, dim3((unsigned)((args.m + 1) / 2)), dim3(128), 0, stream, args);
+    else hipLaunchKernelGGL(warp_kernel<16>, dim3((unsigned)((args.m + 15) / 16)), dim3(128), 0, stream, args);
     return hipGetLastError();
 }
 

@@ -164,3 +164,27 @@ def test_diagnostic_library_is_the_release_surface_plus_debug_entries():
     v = C.c_int(-1)
     assert lib.dsdtm_debug_get_option(b"no_team", C.byref(v)) == 0 and v.value == 0
     assert lib.dsdtm_debug_get_option(b"no_such_switch", C.byref(v)) == capi.ERR_INVALID
+
+
+KEPT_SWITCHES = ("no_team", "ws_no_sort", "ws_no_duo", "no_recover", "fmd_split", "pyr_fused", "pyr_band", "team_no_wrap_clear", "fmd_no_xcd")
+RETIRED_SWITCHES = ("a2d_tree", "a2d_group", "match_group", "warp_group", "po_no_cache", "po_rows", "no_zero_copy", "team_min",
+                    "team_spread_min", "ws_from", "ws_no_windows")
+
+
+def test_diagnostic_library_knows_the_kept_switches_only():
+    """The switches a test, a sanitizer scenario or a kernel argument still uses answer; the A/B switches that rounds 2-6
+    settled (profiles/: "measured and not kept") are unknown keys, to the C entry and to capi.debug_options alike."""
+    lib = capi.load(diag=True)
+    v = C.c_int(-1)
+    for key in KEPT_SWITCHES:
+        assert lib.dsdtm_debug_get_option(key.encode(), C.byref(v)) == capi.OK, key
+    for key in RETIRED_SWITCHES:
+        assert lib.dsdtm_debug_get_option(key.encode(), C.byref(v)) == capi.ERR_INVALID, key
+        assert lib.dsdtm_debug_set_option(key.encode(), 1) == capi.ERR_INVALID, key
+    with pytest.raises(KeyError):
+        with capi.debug_options(a2d_tree=1):
+            pass
+    # exactly those nine: the environment names the library holds are the kept switches' and no others
+    import subprocess
+    strings = subprocess.run(["strings", "-n", "6", capi.lib_path(diag=True)], capture_output=True, text=True, check=True).stdout
+    assert set(re.findall(r"\bDSDTM_[A-Z0-9_]+", strings)) == {"DSDTM_" + k.upper() for k in KEPT_SWITCHES}

@@ -1,6 +1,7 @@
-"""FindMatchDirect for many current frames (warp prelude + Align2D): device time per call by workgroup shape of the warp
-prelude (DSDTM_WARP_GROUP candidates per 128-thread group) — bench.py's FindMatchDirect entry without the rest of the line.
-    python tools/fmd_bench.py [groups ...]          default: 0 (auto) 2 8 16 32 64
+"""FindMatchDirect (warp prelude + Align2D in one launch): device time per call for 64 current frames x 800 candidates —
+bench.py's FindMatchDirect entry without the rest of the line, for the counter passes of tools/fmd_traffic.sh — and for one
+frame's 816 candidates, which bench.py does not time.
+    python tools/fmd_bench.py
 """
 import ctypes as C
 import os
@@ -16,9 +17,8 @@ from dsdtm_amd import capi, synth  # noqa: E402
 
 
 def main():
-    groups = [int(v) for v in sys.argv[1:]] or [0, 2, 8, 16, 32, 64]
     dev = torch.device("cuda", 0)
-    ctx = capi.Context(0, diag=True)   # the diagnostic library (dsdtm_debug_* / switches)
+    ctx = capi.Context(0)
     stream = torch.cuda.Stream(device=dev)
     tdev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     for nfm, ncand in ((64, 800), (1, 816)):
@@ -58,24 +58,17 @@ def main():
                 ctx.handle, d_cur.data_ptr(), nfm, d_kf.data_ptr(), nfm, pitch, Lm, wa, ha, sa, oa, C.byref(cam_m), d_Tk.data_ptr(), d_Tc.data_ptr(),
                 d_fr.data_ptr(), d_kfi.data_ptr(), d_rp.data_ptr(), d_rl.data_ptr(), d_rb.data_ptr(), d_pw.data_ptr(), Lm - 3, 10, Mm,
                 d_scr.data_ptr(), d_px.data_ptr(), d_sl.data_ptr(), d_cv.data_ptr(), stream.cuda_stream))
-        ref = None
-        for g in groups:
-            ctx.check(ctx.lib.dsdtm_debug_set_option(b"warp_group", g))
-            ev = []
-            with torch.cuda.stream(stream):
-                for k in range(33):
-                    d_px.copy_(d_px0, non_blocking=True)
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record(stream); fmd(); b.record(stream)
-                    ev.append((a, b))
-            stream.synchronize()
-            t = [a.elapsed_time(b) for a, b in ev][3:]
-            out = (d_px.cpu().numpy().copy(), d_sl.cpu().numpy().copy(), d_cv.cpu().numpy().copy())
-            same = ref is None or all(np.array_equal(x, y, equal_nan=True) for x, y in zip(out, ref))
-            ref = ref or out
-            print(f"{nfm} frames x {ncand} candidates, warp group {g:2d}: {np.median(t) * 1e3:7.1f} us per call (min {np.min(t) * 1e3:.1f}); "
-                  f"{Mm / np.median(t) / 1e3:.0f} M candidates/s; outputs identical to the first row: {same}", flush=True)
-        ctx.check(ctx.lib.dsdtm_debug_set_option(b"warp_group", 0))
+        ev = []
+        with torch.cuda.stream(stream):
+            for k in range(33):
+                d_px.copy_(d_px0, non_blocking=True)
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(stream); fmd(); b.record(stream)
+                ev.append((a, b))
+        stream.synchronize()
+        t = [a.elapsed_time(b) for a, b in ev][3:]
+        print(f"{nfm} frames x {ncand} candidates: {np.median(t) * 1e3:7.1f} us per call (min {np.min(t) * 1e3:.1f}); "
+              f"{Mm / np.median(t) / 1e3:.0f} M candidates/s; converged {d_cv.float().mean().item():.3f}", flush=True)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ REPO="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$REPO/gpurun_out/${1:-fmdtraffic}"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 5 200 rocprofv3 --pmc $c --output-format csv -d "$OUT/$c" -- python3 $REPO/tools/fmd_bench.py 0 > "$OUT/$c.log" 2>&1 || echo "pass $c failed"
+  timeout -k 5 200 rocprofv3 --pmc $c --output-format csv -d "$OUT/$c" -- python3 $REPO/tools/fmd_bench.py > "$OUT/$c.log" 2>&1 || echo "pass $c failed"
 done
 cd "$REPO"
 python3 - "$OUT" <<'PY'

@@ -1,6 +1,7 @@
 #!/bin/bash
 # rocprofv3 passes behind profiles/r06_*: kernel trace + stats, then one counter group per pass (never --pmc
-# together with other trace domains). Usage on the GPU box: tools/profile.sh <outdir-under-gpurun_out>
+# together with other trace domains); every pass has its own time limit and the first one that fails ends the script.
+# Usage on the GPU box: tools/profile.sh <name of the output directory> ["<cases>"]
 # Each "case" is one command line; cases: main (bench defaults: 8 launch streams), solo (one stream), n1000, n2000, the
 # secondary kernels (tools/kernels.py: pyrDown, Align2D), one tracked frame (tools/track_step.py: pyramid, single-pair
 # alignment, warp prelude, Align2D, pose refinement, detector) and the batched pose refinement (tools/pose_opt_bench.py).
@@ -28,21 +29,21 @@ CASE[poseopt]="$REPO/tools/pose_opt_bench.py 4096 200 nolatency"
 CASE[secondary]="$REPO/bench.py --full --steps 5 --warmup 2 --preroll 0 --no-cpu"
 for c in $CASES; do
   mkdir -p "$OUT/$c"
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$c/trace" -- python3 ${CASE[$c]} > "$OUT/$c/trace.log" 2>&1 || echo "trace $c failed"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$c/trace" -- python3 ${CASE[$c]} > "$OUT/$c/trace.log" 2>&1 || { echo "trace $c failed"; exit 1; }
   echo "traced $c"
 done
 for c in $CASES; do
   [ "$c" = main ] && continue
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/$c/pmc_fetch" -- python3 ${CASE[$c]} > "$OUT/$c/pmc_fetch.log" 2>&1 || echo "pmc fetch $c failed"
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/$c/pmc_write" -- python3 ${CASE[$c]} > "$OUT/$c/pmc_write.log" 2>&1 || echo "pmc write $c failed"
+  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/$c/pmc_fetch" -- python3 ${CASE[$c]} > "$OUT/$c/pmc_fetch.log" 2>&1 || { echo "pmc fetch $c failed"; exit 1; }
+  timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/$c/pmc_write" -- python3 ${CASE[$c]} > "$OUT/$c/pmc_write.log" 2>&1 || { echo "pmc write $c failed"; exit 1; }
   echo "counted $c"
 done
 for c in solo n1000 n2000 poseopt; do
   has $c || continue
-  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d "$OUT/$c/pmc_sq" -- python3 ${CASE[$c]} > "$OUT/$c/pmc_sq.log" 2>&1 || echo "pmc sq $c failed"
+  timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d "$OUT/$c/pmc_sq" -- python3 ${CASE[$c]} > "$OUT/$c/pmc_sq.log" 2>&1 || { echo "pmc sq $c failed"; exit 1; }
 done
 # FP64 instruction mix of the alignment kernel (bench.py's fp64 block: flops per launch = 64 x (ADD + MUL + 2 FMA + TRANS))
-if has solo; then timeout -k 5 300 rocprofv3 --pmc SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT32 --output-format csv -d "$OUT/solo/pmc_fp64" -- python3 ${CASE[solo]} > "$OUT/solo/pmc_fp64.log" 2>&1 || echo "pmc fp64 failed"; fi
+if has solo; then timeout -k 5 300 rocprofv3 --pmc SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT32 --output-format csv -d "$OUT/solo/pmc_fp64" -- python3 ${CASE[solo]} > "$OUT/solo/pmc_fp64.log" 2>&1 || { echo "pmc fp64 failed"; exit 1; }; fi
 # keep the merge-back small: the per-dispatch CSVs of the long runs are summarised on the box
 cd "$REPO"
 python3 tools/summarize_profile.py "$OUT" > "$OUT/summary.txt" 2>&1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One variant of the library under the one-call tracked frame: wall clock (pinned and pageable image) and the mean duration of
-# every kernel of a frame from a rocprofv3 kernel trace. Used through tools/ab_lib.sh for same-box A/B:
-#   tools/ab_lib.sh tools/track_trace.sh variants/lib_a.so variants/lib_b.so
+# every kernel of a frame from a rocprofv3 kernel trace. Run once per library build on the same visit for a same-box A/B:
+#   tools/track_trace.sh <label>
 label="${1:-current}"
 REPO="$(cd "$(dirname "$0")/.." && pwd)"
 export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 """Where a launch of the large-pair kernels spends its time: the config-3 / config-5 batches at iteration caps 1 and 10
 (cap 1 = four level starts with their first pass, H pass and solve; the difference = the later iterations). One line
-per shape and cap; run once per library build in the same gpurun call (tools/ab_lib.sh) for same-box comparisons.
+per shape and cap; run once per library build on the same visit for same-box comparisons.
 
     python tools/ws_cap.py [label]
 """
