@@ -144,6 +144,10 @@ EXPORTED_SYMBOLS = [
     "dsdtm_track_frames", "dsdtm_local_ba", "dsdtm_local_ba_batch_device",
     "dsdtm_frame_prefetch", "dsdtm_frame_wait", "dsdtm_track_frame_on", "dsdtm_frame_lift",
 ]
+# every symbol include/dsdtm_amd_keyframe.h declares: the add-on library (Tracking::NeedKeyframe for n trackers), loaded on first use
+KEYFRAME_SYMBOLS = ["dsdtm_keyframe_create", "dsdtm_keyframe_destroy", "dsdtm_keyframe_last_error", "dsdtm_need_keyframe",
+                    "dsdtm_need_keyframes"]
+KEYFRAME_LIB_NAME = "libdsdtm_amd_keyframe.so"
 
 
 class DetectParams(C.Structure):
@@ -213,6 +217,38 @@ class FrameImage(C.Structure):
 
 
 LIFT_MAX = 16384
+KF_MAX_POINTS, KF_MAX_LOCAL_KF, TRACK_FRAMES_MAX = 4096, 64, 1024
+
+
+class KeyframeParams(C.Structure):
+    """dsdtm_keyframe_params: the thresholds of Tracking::NeedKeyframe (src/Tracking.cpp:347-410)."""
+    _fields_ = [("min_valid", C.c_int32), ("max_valid", C.c_int32), ("px_samples", C.c_int32), ("reserved", C.c_int32),
+                ("min_px_median", C.c_double), ("min_rot", C.c_double), ("min_trans", C.c_double)]
+
+
+class KeyframeDesc(C.Structure):
+    """dsdtm_keyframe_desc: one tracker's inputs of dsdtm_need_keyframes."""
+    _fields_ = [("T_cur_w", C.c_void_p), ("T_kf_w", C.c_void_p), ("n_valid", C.c_int32),
+                ("n_cur_points", C.c_int32), ("cur_p_world", C.c_void_p), ("cur_bad", C.c_void_p),
+                ("n_kf_points", C.c_int32), ("kf_p_world", C.c_void_p), ("kf_bad", C.c_void_p),
+                ("n_local_kf", C.c_int32), ("local_kf_centre", C.c_void_p)]
+
+
+class KeyframeVerdict(C.Structure):
+    _fields_ = [("need", C.c_int32), ("reason", C.c_int32), ("rule_mask", C.c_int32), ("undefined", C.c_int32),
+                ("n_px", C.c_int32), ("n_depth", C.c_int32), ("svo_kf", C.c_int32), ("reserved", C.c_int32),
+                ("median_px", C.c_double), ("rot", C.c_double), ("trans", C.c_double),
+                ("min_depth", C.c_double), ("median_depth", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+KEYFRAME_VERDICT_DTYPE = np.dtype([("need", "<i4"), ("reason", "<i4"), ("rule_mask", "<i4"), ("undefined", "<i4"),
+                                   ("n_px", "<i4"), ("n_depth", "<i4"), ("svo_kf", "<i4"), ("reserved", "<i4"),
+                                   ("median_px", "<f8"), ("rot", "<f8"), ("trans", "<f8"), ("min_depth", "<f8"),
+                                   ("median_depth", "<f8")])
+assert KEYFRAME_VERDICT_DTYPE.itemsize == C.sizeof(KeyframeVerdict)
 
 
 class TrackMatch(C.Structure):
@@ -415,6 +451,147 @@ def track_frames(ctx, cam, n, descs, results, matches, residual_norm, in_grid, f
             results[f].frame = df.handle.value if isinstance(df.handle, C.c_void_p) else df.handle
     return ctx.lib.dsdtm_track_frames(ctx.handle, C.byref(cam) if isinstance(cam, Camera) else C.byref(camera_struct(cam)), n, descs,
                                       results, matches, residual_norm, in_grid)
+
+
+def keyframe_lib_path() -> str:
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", KEYFRAME_LIB_NAME)
+
+
+def load_keyframe():
+    """Load libdsdtm_amd_keyframe.so (include/dsdtm_amd_keyframe.h). No fallback: raises if it has not been built."""
+    if "keyframe" in _LIBS:
+        return _LIBS["keyframe"]
+    path = keyframe_lib_path()
+    if not os.path.exists(path):
+        raise ImportError(f"{path} not found: the HIP extension is not built. Run "
+                          "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). dsdtm_amd has no CPU fallback.")
+    lib = C.CDLL(path)
+    lib.dsdtm_keyframe_create.restype = C.c_int
+    lib.dsdtm_keyframe_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.dsdtm_keyframe_destroy.restype = None
+    lib.dsdtm_keyframe_destroy.argtypes = [C.c_void_p]
+    lib.dsdtm_keyframe_last_error.restype = C.c_char_p
+    lib.dsdtm_keyframe_last_error.argtypes = [C.c_void_p]
+    lib.dsdtm_need_keyframe.restype = C.c_int
+    lib.dsdtm_need_keyframe.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(KeyframeParams), C.POINTER(KeyframeDesc), C.c_void_p]
+    lib.dsdtm_need_keyframes.restype = C.c_int
+    lib.dsdtm_need_keyframes.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(KeyframeParams), C.c_int, C.POINTER(KeyframeDesc),
+                                         C.c_void_p]
+    _LIBS["keyframe"] = lib
+    return lib
+
+
+class KeyframeContext:
+    """A dsdtm_keyframe_ctx: the add-on library's own context (stream + staging block) on one device."""
+
+    def __init__(self, device: int = 0):
+        self.lib = load_keyframe()
+        self.device = device
+        h = C.c_void_p()
+        st = self.lib.dsdtm_keyframe_create(device, C.byref(h))
+        if st != OK:
+            msg = self.lib.dsdtm_keyframe_last_error(None)
+            raise DsdtmError(st, msg.decode() if msg else "")
+        self.handle = h
+
+    def last_error(self) -> str:
+        msg = self.lib.dsdtm_keyframe_last_error(self.handle)
+        return msg.decode() if msg else ""
+
+    def check(self, st: int):
+        if st != OK:
+            raise DsdtmError(st, self.last_error())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.dsdtm_keyframe_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def keyframe_context_of(ctx) -> KeyframeContext:
+    """The keyframe context that goes with a Context (same device; created on first use, kept on the Context); a
+    KeyframeContext is returned as it is."""
+    if isinstance(ctx, KeyframeContext):
+        return ctx
+    kc = getattr(ctx, "_keyframe_ctx", None)
+    if kc is None or kc.handle is None:
+        kc = ctx._keyframe_ctx = KeyframeContext(getattr(ctx, "device", 0))
+    return kc
+
+
+def keyframe_params_struct(params=None) -> KeyframeParams:
+    """dsdtm_keyframe_params from a keyframe_decision.KeyframeParams (or anything with its attributes); None: the defaults."""
+    if isinstance(params, KeyframeParams):
+        return params
+    g = (lambda k, d: d) if params is None else (lambda k, d: getattr(params, k, d))
+    return KeyframeParams(int(g("min_valid", 30)), int(g("max_valid", 50)), int(g("px_samples", 31)), 0,
+                          float(g("min_px_median", 40.0)), float(g("min_rot", 0.08)), float(g("min_trans", 0.08)))
+
+
+class KeyframeCall:
+    """One prepared dsdtm_need_keyframes call: the descriptors and every array they point at are built once, `run_raw()` is the
+    library call alone. `descs`: one dict per tracker with T_cur_w, T_kf_w (12 doubles or 3x4), n_valid, cur_p_world (n x 3),
+    cur_bad (n bytes or None = none bad), kf_p_world, kf_bad, local_kf_centre (n x 3)."""
+
+    def __init__(self, ctx, cam, params, descs, single: bool = False):
+        self.ctx, self.n, self.single = keyframe_context_of(ctx), len(descs), single
+        self.cs = cam if isinstance(cam, Camera) else camera_struct(cam)
+        self.prm = keyframe_params_struct(params)
+        self.descs = (KeyframeDesc * max(1, self.n))()
+        self._keep = []
+
+        def arr(v, dtype, cols):
+            if v is None:
+                return None, 0
+            a = np.ascontiguousarray(v, dtype).reshape((-1, cols) if cols else (-1,))
+            self._keep.append(a)
+            return (a.ctypes.data if a.size else None), len(a)
+
+        for t, d in enumerate(descs):
+            k = self.descs[t]
+            k.T_cur_w, _ = arr(np.asarray(d["T_cur_w"], np.float64).reshape(12), np.float64, 0)
+            k.T_kf_w, _ = arr(np.asarray(d["T_kf_w"], np.float64).reshape(12), np.float64, 0)
+            k.n_valid = int(d["n_valid"])
+            k.cur_p_world, k.n_cur_points = arr(d["cur_p_world"], np.float64, 3)
+            k.cur_bad, nb = arr(d.get("cur_bad"), np.uint8, 0)
+            if d.get("cur_bad") is not None and nb != k.n_cur_points:
+                raise ValueError(f"tracker {t}: {nb} cur_bad flags for {k.n_cur_points} points")
+            k.kf_p_world, k.n_kf_points = arr(d["kf_p_world"], np.float64, 3)
+            k.kf_bad, nb = arr(d.get("kf_bad"), np.uint8, 0)
+            if d.get("kf_bad") is not None and nb != k.n_kf_points:
+                raise ValueError(f"tracker {t}: {nb} kf_bad flags for {k.n_kf_points} points")
+            k.local_kf_centre, k.n_local_kf = arr(d["local_kf_centre"], np.float64, 3)
+        self.verdicts = np.zeros(max(1, self.n), KEYFRAME_VERDICT_DTYPE)
+
+    def run_raw(self) -> int:
+        if self.single:
+            return self.ctx.lib.dsdtm_need_keyframe(self.ctx.handle, C.byref(self.cs), C.byref(self.prm), self.descs, self.verdicts.ctypes.data)
+        return self.ctx.lib.dsdtm_need_keyframes(self.ctx.handle, C.byref(self.cs), C.byref(self.prm), self.n, self.descs,
+                                                 self.verdicts.ctypes.data)
+
+    def run(self) -> list:
+        self.ctx.check(self.run_raw())
+        return [{k: self.verdicts[k][t].item() for k in KEYFRAME_VERDICT_DTYPE.names if k != "reserved"} for t in range(self.n)]
+
+
+def need_keyframes(ctx, cam, params, descs) -> list:
+    """dsdtm_need_keyframes: Tracking::NeedKeyframe (src/Tracking.cpp:347-410) for len(descs) independent trackers in one
+    submission (`ctx`: a Context, whose keyframe context is made on first use, or a KeyframeContext). Returns one dict per tracker: need, reason, rule_mask, undefined, n_px, n_depth, svo_kf, median_px, rot, trans,
+    min_depth, median_depth (the fields of dsdtm_keyframe_verdict)."""
+    if not descs:
+        return []
+    return KeyframeCall(ctx, cam, params, descs).run()
+
+
+def need_keyframe(ctx, cam, params, desc) -> dict:
+    """dsdtm_need_keyframe: the batch entry with n = 1."""
+    return KeyframeCall(ctx, cam, params, [desc], single=True).run()[0]
 
 
 def device_frame_of(ctx, frame):

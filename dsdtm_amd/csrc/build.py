@@ -29,6 +29,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["api.cpp", "sparse_align.hip", "align2d.hip", "pyrdown.hip", "warp.hip", "match.hip", "detect.hip", "pose_opt.hip", "track.hip", "local_ba.hip", "rgbd.hip"]
 DIAG_SOURCES = ["selftest.hip"]                      # diagnostic build only
 HEADERS = ["kernels.h", "device_math.h", "warp_body.h", "align2d_body.h", "match_body.h", "pose_math.h", "exports.map", os.path.join("..", "..", "include", "dsdtm_amd.h")]
+# the add-on library (include/dsdtm_amd_keyframe.h: Tracking::NeedKeyframe for n trackers): sources and headers of its own, so that
+# libdsdtm_amd.so — its symbols, its source hash — is untouched by it; built by build_all() with the release flags
+KEYFRAME_SOURCES = ["keyframe_api.cpp", "keyframe.hip"]
+KEYFRAME_HEADERS = ["keyframe.h", "device_math.h", "pose_math.h", "exports.map", os.path.join("..", "..", "include", "dsdtm_amd_keyframe.h"),
+                    os.path.join("..", "..", "include", "dsdtm_amd.h")]
+OUT_KEYFRAME = os.path.join(HERE, "libdsdtm_amd_keyframe.so")
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")
 TAG = OUT + ".tag"
@@ -124,8 +130,28 @@ def build(force=False, verbose=True, extra=(), diag=False):
     return out
 
 
+def build_keyframe(force=False, verbose=True):
+    """libdsdtm_amd_keyframe.so: the add-on's two sources, each to its own object, linked through the same version script."""
+    flags = _flags([])
+    hipcc = os.environ.get("HIPCC", "hipcc")
+    hdrs = [os.path.join(HERE, h) for h in KEYFRAME_HEADERS] + [os.path.abspath(__file__)]
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    objs = [_obj(s, flags) for s in KEYFRAME_SOURCES]
+    jobs = [[hipcc, *flags, "-x", "hip", "-c", os.path.join(HERE, s), "-o", o] for s, o in zip(KEYFRAME_SOURCES, objs)
+            if force or _stale(o, [os.path.join(HERE, s)] + hdrs)]
+    if not jobs and not _stale(OUT_KEYFRAME, objs) and not force:
+        return OUT_KEYFRAME
+    for cmd in jobs + [[hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-fno-gpu-rdc",
+                        "-Wl,--version-script=" + os.path.join(HERE, "exports.map"), *objs, "-o", OUT_KEYFRAME]]:
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True, cwd=HERE)
+    return OUT_KEYFRAME
+
+
 def build_all(force=False, verbose=True):
-    """The release library and the diagnostic one (what __graft_entry__.build() and the test session build)."""
+    """The release library and the diagnostic one (what __graft_entry__.build() and the test session build), and the add-on."""
+    build_keyframe(force, verbose)
     return build(force, verbose), build(force, verbose, diag=True)
 
 
@@ -142,3 +168,5 @@ if __name__ == "__main__":
         print(build(a.force, extra=extra))
     if a.all or a.diag:
         print(build(a.force, extra=extra, diag=True))
+    if a.all:
+        print(build_keyframe(a.force))

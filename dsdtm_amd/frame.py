@@ -24,6 +24,8 @@ class Config:
         "Camera.Max_fts": 200,         # src/Feature_detection.cpp:14 (Config/EuRoc.yaml:27)
         "Camera.Min_dist": 30,         # src/Frame.cpp:52 (Config/EuRoc.yaml:28)
         "Optimization.LocalBAthreshhold": 2.0,   # src/Optimizer.cpp:22 (Config/default.yaml:94)
+        "KeyFrame.min_rot": 0.08,      # src/Tracking.cpp:26 (Config/default.yaml:97)
+        "KeyFrame.min_trans": 0.08,    # src/Tracking.cpp:27 (Config/default.yaml:98)
     }
 
     @classmethod

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/dsdtm_amd.h"
+#include "../../include/dsdtm_amd_keyframe.h"   // declarations only: libdsdtm_amd_keyframe.so is needed by Tracking::NeedKeyframeOnDevice alone
 
 namespace DSDTM {
 
@@ -594,6 +595,124 @@ public:
     }
 };
 
+// ---- Tracking::NeedKeyframe on the host (src/Tracking.cpp:347-410) -----------------------------------------
+// The rules of dsdtm_need_keyframes (include/dsdtm_amd_keyframe.h documents each with its quirks) evaluated here, with NO device
+// call: the right choice for ONE tracker — a device round trip costs more than these few hundred transforms — and the
+// baseline the batch entry is measured against (README). Same inputs, same verdict fields. Every product and sum
+// rounds on its own when this header is compiled without FMA contraction (-ffp-contract=off; the x86-64 default).
+namespace detail {
+struct KfQuat { double w, x, y, z, tx, ty, tz; };          // Sophus::SE3: unit quaternion + translation
+inline void kf_normalize(KfQuat& q) {                     // (the library's normalisation: csrc/device_math.h)
+    const double n2 = q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z, e = n2 - 1.0;
+    const double rn = std::fabs(e) < 1e-5 ? 1.0 + e * (-0.5 + 0.375 * e) : 1.0 / std::sqrt(n2);
+    q.w *= rn; q.x *= rn; q.y *= rn; q.z *= rn;
+}
+inline void kf_rotate(const KfQuat& q, double vx, double vy, double vz, double& ox, double& oy, double& oz) {
+    double ux = q.y * vz - q.z * vy, uy = q.z * vx - q.x * vz, uz = q.x * vy - q.y * vx;
+    ux += ux; uy += uy; uz += uz;
+    const double cx = q.y * uz - q.z * uy, cy = q.z * ux - q.x * uz, cz = q.x * uy - q.y * ux;
+    ox = vx + q.w * ux + cx; oy = vy + q.w * uy + cy; oz = vz + q.w * uz + cz;
+}
+inline KfQuat kf_from_rt(const double* T) {               // Eigen: rotation matrix -> quaternion, then normalise
+    const double m00 = T[0], m01 = T[1], m02 = T[2], m10 = T[4], m11 = T[5], m12 = T[6], m20 = T[8], m21 = T[9], m22 = T[10];
+    KfQuat o;
+    double t = m00 + m11 + m22;
+    if (t > 0.0) { t = std::sqrt(t + 1.0); o.w = 0.5 * t; t = 0.5 / t; o.x = (m21 - m12) * t; o.y = (m02 - m20) * t; o.z = (m10 - m01) * t; }
+    else if (m00 >= m11 && m00 >= m22) { t = std::sqrt(m00 - m11 - m22 + 1.0); o.x = 0.5 * t; t = 0.5 / t; o.w = (m21 - m12) * t; o.y = (m10 + m01) * t; o.z = (m20 + m02) * t; }
+    else if (m11 > m00 && m11 >= m22) { t = std::sqrt(m11 - m22 - m00 + 1.0); o.y = 0.5 * t; t = 0.5 / t; o.w = (m02 - m20) * t; o.z = (m21 + m12) * t; o.x = (m01 + m10) * t; }
+    else { t = std::sqrt(m22 - m00 - m11 + 1.0); o.z = 0.5 * t; t = 0.5 / t; o.w = (m10 - m01) * t; o.x = (m02 + m20) * t; o.y = (m12 + m21) * t; }
+    kf_normalize(o);
+    o.tx = T[3]; o.ty = T[7]; o.tz = T[11];
+    return o;
+}
+inline KfQuat kf_inverse(const KfQuat& a) {
+    KfQuat r; r.w = a.w; r.x = -a.x; r.y = -a.y; r.z = -a.z;
+    kf_rotate(r, -a.tx, -a.ty, -a.tz, r.tx, r.ty, r.tz);
+    return r;
+}
+inline KfQuat kf_mul(const KfQuat& a, const KfQuat& b) {
+    KfQuat r; double rx, ry, rz;
+    kf_rotate(a, b.tx, b.ty, b.tz, rx, ry, rz);
+    r.tx = a.tx + rx; r.ty = a.ty + ry; r.tz = a.tz + rz;
+    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
+    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
+    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
+    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
+    kf_normalize(r);
+    return r;
+}
+inline void kf_transform(const double* m, const double* P, double& x, double& y, double& z) {
+    x = m[0] * P[0] + m[1] * P[1] + m[2] * P[2] + m[3];
+    y = m[4] * P[0] + m[5] * P[1] + m[6] * P[2] + m[7];
+    z = m[8] * P[0] + m[9] * P[1] + m[10] * P[2] + m[11];
+}
+inline double kf_median(std::vector<double>& v) {         // utils::GetMedian (include/Utils.h:34-40): the UPPER middle
+    std::nth_element(v.begin(), v.begin() + (std::ptrdiff_t)(v.size() / 2), v.end());
+    return v[v.size() / 2];
+}
+}  // namespace detail
+
+inline dsdtm_keyframe_params DefaultKeyframeParams(double min_rot, double min_trans) {   // src/Tracking.cpp:26-27, :354, :374, :378
+    dsdtm_keyframe_params p{};
+    p.min_valid = 30; p.max_valid = 50; p.px_samples = 31; p.min_px_median = 40.0; p.min_rot = min_rot; p.min_trans = min_trans;
+    return p;
+}
+
+inline void need_keyframe_host(const dsdtm_camera& cam, const dsdtm_keyframe_params& prm, const dsdtm_keyframe_desc& d,
+                               dsdtm_keyframe_verdict* out) {
+    const double fx = (double)cam.fx, fy = (double)cam.fy, cx = (double)cam.cx, cy = (double)cam.cy;
+    const double *Tc = d.T_cur_w, *Tk = d.T_kf_w;
+    int mask = 0;
+    bool undefined = false;
+    if (d.n_valid >= prm.min_valid && d.n_valid <= prm.max_valid) mask |= 1;                       // K1 (:354)
+    std::vector<double> px;                                                                        // K2 (:359-381)
+    for (int i = 0; i < d.n_kf_points && (int)px.size() < prm.px_samples; ++i) {
+        if (d.kf_bad && d.kf_bad[i]) continue;
+        double x, y, z;
+        detail::kf_transform(Tc, d.kf_p_world + 3 * (size_t)i, x, y, z);
+        const double u1 = fx * x / z + cx, v1 = fy * y / z + cy;
+        detail::kf_transform(Tk, d.kf_p_world + 3 * (size_t)i, x, y, z);
+        const double u2 = fx * x / z + cx, v2 = fy * y / z + cy;
+        const double du = u1 - u2, dv = v1 - v2;
+        px.push_back(std::sqrt(du * du + dv * dv));
+        undefined = undefined || !std::isfinite(px.back());
+    }
+    const int n_px = (int)px.size();
+    const double median_px = (n_px > 0 && !undefined) ? detail::kf_median(px) : 0.0;
+    if (n_px > 0 && median_px > prm.min_px_median) mask |= 2;
+    const detail::KfQuat D = detail::kf_mul(detail::kf_inverse(detail::kf_from_rt(Tk)), detail::kf_from_rt(Tc));   // K3 (:384-390)
+    const double n = std::sqrt(D.x * D.x + D.y * D.y + D.z * D.z);
+    const double f = n < 1e-10 ? 2. / D.w - 2. * (n * n) / (D.w * (D.w * D.w)) : 2 * std::atan(n / D.w) / n;   // Sophus SO3::log
+    const double w0 = f * D.x, w1 = f * D.y, w2 = f * D.z;
+    const double rot = std::sqrt(w0 * w0 + w1 * w1 + w2 * w2), trans = std::sqrt(D.tx * D.tx + D.ty * D.ty + D.tz * D.tz);
+    if (rot >= prm.min_rot || trans >= prm.min_trans) mask |= 4;
+    std::vector<double> depth;                                                                     // K4 (:393-402)
+    double zmin = 1.7976931348623157e308;
+    bool depth_nonfinite = false;
+    for (int i = 0; i < d.n_cur_points; ++i) {
+        if (d.cur_bad && d.cur_bad[i]) continue;
+        double x, y, z;
+        detail::kf_transform(Tc, d.cur_p_world + 3 * (size_t)i, x, y, z);
+        depth.push_back(z);
+        zmin = std::fmin(zmin, z);
+        depth_nonfinite = depth_nonfinite || !std::isfinite(z);
+    }
+    undefined = undefined || depth_nonfinite;
+    const int n_depth = (int)depth.size();
+    const double m = (n_depth > 0 && !depth_nonfinite) ? detail::kf_median(depth) : 0.0;
+    int svo = -1;
+    if (n_depth > 0 && !undefined)
+        for (int j = 0; j < d.n_local_kf; ++j) {
+            double x, y, z;
+            detail::kf_transform(Tc, d.local_kf_centre + 3 * (size_t)j, x, y, z);
+            if (x / m >= m && y / m >= m * 0.8 && z / m >= m * 1.3) { svo = j; break; }            // fabs(a >= b): no absolute value
+        }
+    if (svo >= 0) mask |= 8;
+    out->need = mask != 0; out->reason = (mask & 1) ? 1 : (mask & 2) ? 2 : (mask & 4) ? 3 : (mask & 8) ? 4 : 0;
+    out->rule_mask = mask; out->undefined = undefined ? 1 : 0; out->n_px = n_px; out->n_depth = n_depth; out->svo_kf = svo; out->reserved = 0;
+    out->median_px = median_px; out->rot = rot; out->trans = trans; out->min_depth = n_depth > 0 ? zmin : 0.0; out->median_depth = m;
+}
+
 // ---- one tracked frame in ONE library call (src/Tracking.cpp:199-256) --------------------------------------
 // Tracking::TrackWithLastFrame + UpdateLocalMap + TrackWithLocalMap for a tracker whose frames live on the device:
 // dsdtm_track_frame enqueues the new frame's upload and pyramid, Run, ReprojectPoint + Get_ClosetObs for every local map
@@ -699,6 +818,55 @@ public:
                 if (!mp->IsBad()) mp->EraseFound();
             }
         return cur;
+    }
+
+    // Tracking::NeedKeyframe (:347-410) for the frame TrackFrame returned: the map points of `cur` and of the last keyframe in
+    // mvFeatures order (features without a map point are not in the lists), Get_VaildMpNums() (src/Frame.cpp:330-340) and the
+    // camera centres of mvpLocalKeyFrames, through need_keyframe_host — no device call, no further library: the faster path at
+    // every batch size measured (README). NeedKeyframeOnDevice is the same decision through dsdtm_need_keyframe of the add-on
+    // library libdsdtm_amd_keyframe.so (link it when this is called); the batch entry dsdtm_need_keyframes takes n KeyframeInputs.
+    struct KeyframeInputs {
+        std::vector<double> pc, pk, cen;
+        std::vector<uint8_t> bc, bk;
+        dsdtm_keyframe_desc d{};
+        dsdtm_camera cam{};
+    };
+    void GatherKeyframeInputs(const Frame& cur, const Frame& last_kf, const std::vector<Frame*>& local_keyframes, KeyframeInputs* in) const {
+        int n_valid = 0;
+        for (const Feature& f : cur.mvFeatures) {
+            if (!f.Mpt) continue;
+            ++n_valid;
+            in->pc.insert(in->pc.end(), f.Mpt->Get_Pose().begin(), f.Mpt->Get_Pose().end()); in->bc.push_back(f.Mpt->IsBad() ? 1 : 0);
+        }
+        for (const Feature& f : last_kf.mvFeatures) {
+            if (!f.Mpt) continue;
+            in->pk.insert(in->pk.end(), f.Mpt->Get_Pose().begin(), f.Mpt->Get_Pose().end()); in->bk.push_back(f.Mpt->IsBad() ? 1 : 0);
+        }
+        for (const Frame* k : local_keyframes) { const std::array<double, 3> c = k->Get_CameraCnt(); in->cen.insert(in->cen.end(), c.begin(), c.end()); }
+        dsdtm_keyframe_desc& d = in->d;
+        d.T_cur_w = cur.Get_Pose().m.data(); d.T_kf_w = last_kf.Get_Pose().m.data(); d.n_valid = n_valid;
+        d.n_cur_points = (int32_t)in->bc.size(); d.cur_p_world = in->pc.data(); d.cur_bad = in->bc.data();
+        d.n_kf_points = (int32_t)in->bk.size(); d.kf_p_world = in->pk.data(); d.kf_bad = in->bk.data();
+        d.n_local_kf = (int32_t)local_keyframes.size(); d.local_kf_centre = in->cen.data();
+        const Camera& c = *mCam;
+        in->cam = dsdtm_camera{c.mfx, c.mfy, c.mcx, c.mcy, c.mf, c.mwidth, c.mheight};
+    }
+    dsdtm_keyframe_verdict NeedKeyframe(const Frame& cur, const Frame& last_kf, const std::vector<Frame*>& local_keyframes,
+                                        const dsdtm_keyframe_params& prm) const {
+        KeyframeInputs in;
+        GatherKeyframeInputs(cur, last_kf, local_keyframes, &in);
+        dsdtm_keyframe_verdict v{};
+        need_keyframe_host(in.cam, prm, in.d, &v);
+        return v;
+    }
+    dsdtm_keyframe_verdict NeedKeyframeOnDevice(dsdtm_keyframe_ctx* kctx, const Frame& cur, const Frame& last_kf,
+                                                const std::vector<Frame*>& local_keyframes, const dsdtm_keyframe_params& prm) const {
+        KeyframeInputs in;
+        GatherKeyframeInputs(cur, last_kf, local_keyframes, &in);
+        dsdtm_keyframe_verdict v{};
+        if (dsdtm_need_keyframe(kctx, &in.cam, &prm, &in.d, &v) != DSDTM_OK)
+            throw std::runtime_error(std::string("dsdtm_need_keyframe: ") + dsdtm_keyframe_last_error(kctx));
+        return v;
     }
 
 private:

@@ -7,6 +7,7 @@
 // behind (map point, mbInitial, bearing). Reads a world + frame sequence written by tests/test_host_cpp.py.
 //   usage: example_track <world.bin> [onecall]     onecall: every frame through ONE dsdtm_track_frame (Tracking::TrackFrame of the
 //                                                  host layer) instead of the four synchronous calls — the same lines are printed
+//          example_track <world.bin> onecall keyframe   + one line per frame: Tracking::NeedKeyframe (host evaluation) against the last keyframe
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -77,6 +78,8 @@ int main(int argc, char** argv) {
     FramePtr last = kfs.back();
     const bool onecall = argc > 2 && std::string(argv[2]) == "onecall";
     Tracking tracker(cam, 5, 0, 8, 20);
+    const bool keyframe = argc > 3 && std::string(argv[3]) == "keyframe";
+    const dsdtm_keyframe_params kprm = DefaultKeyframeParams(0.08, 0.08);      // KeyFrame.min_rot / min_trans (Config/default.yaml)
     for (int k = 0; k < n_frames && onecall; ++k) {
         Image8 im(W, H);
         rd(f, im.data.data(), im.data.size());
@@ -93,6 +96,11 @@ int main(int argc, char** argv) {
         std::printf("\nmap");
         for (const MapPoint& mp : mps) std::printf(" %d%s", mp.mnFound, mp.mbBad ? "b" : "");
         std::printf("\n");
+        if (keyframe) {                                                        // src/Tracking.cpp:347-410, after PoseOptimization
+            const dsdtm_keyframe_verdict v = tracker.NeedKeyframe(*cur, *kfs.back(), kfp, kprm);
+            std::printf("keyframe %d reason %d mask %d px %d %.17g rot %.17g trans %.17g depth %d %.17g %.17g svo %d\n", v.need, v.reason,
+                        v.rule_mask, v.n_px, v.median_px, v.rot, v.trans, v.n_depth, v.min_depth, v.median_depth, v.svo_kf);
+        }
         last = cur;
     }
     for (int k = 0; k < n_frames && !onecall; ++k) {

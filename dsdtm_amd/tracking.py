@@ -18,6 +18,7 @@ import numpy as np
 
 from . import capi, search
 from .frame import Config, Frame
+from .keyframe_decision import KeyframeParams
 
 
 def flatten_local_map(keyframes, map_points):
@@ -217,6 +218,35 @@ def apply_tracked_frame(cam, image, r, map_points, img_mask=None):
     return cur, r["n_tracked"], [(int(m["cell"][k]), mps[k], m["px"][k].copy(), int(m["level"][k])) for k in range(len(m))]
 
 
+def frame_map_points(frame) -> list:
+    """The frame's map points in feature order, as NeedKeyframe and Get_SceneDepth walk them (`for it in mvFeatures: if
+    (!(*it)->Mpt) continue`, src/Tracking.cpp:360-363, src/Frame.cpp:248-251): from reference-shaped features (objects with an
+    `Mpt`), else from the mirror's mvMapPoints (one entry per feature, None where the feature has no map point)."""
+    fts = getattr(frame, "mvFeatures", None)
+    if fts is not None and all(hasattr(f, "Mpt") for f in fts):
+        return [f.Mpt for f in fts if f.Mpt is not None]
+    return [mp for mp in getattr(frame, "mvMapPoints", []) if mp is not None]
+
+
+def keyframe_desc(cur, last_kf, local_keyframes) -> dict:
+    """One tracker's inputs of dsdtm_need_keyframes (capi.KeyframeCall) from reference-shaped Frame / KeyFrame / MapPoint
+    objects: both poses, Get_VaildMpNums() (src/Frame.cpp:330-340: the features that have a map point), the map points of the
+    current frame and of the last keyframe in feature order with their IsBad(), the camera centres of mvpLocalKeyFrames."""
+    def centre(kf):
+        if hasattr(kf, "Get_CameraCnt"):
+            return np.asarray(kf.Get_CameraCnt(), np.float64)
+        T = np.asarray(kf.Get_Pose(), np.float64).reshape(3, 4)
+        return -T[:, :3].T @ T[:, 3]
+    mc, mk = frame_map_points(cur), frame_map_points(last_kf)
+    return dict(T_cur_w=np.asarray(cur.Get_Pose(), np.float64).reshape(12), T_kf_w=np.asarray(last_kf.Get_Pose(), np.float64).reshape(12),
+                n_valid=len(mc),
+                cur_p_world=np.array([mp.Get_Pose() for mp in mc], np.float64).reshape(-1, 3),
+                cur_bad=np.array([1 if mp.IsBad() else 0 for mp in mc], np.uint8),
+                kf_p_world=np.array([mp.Get_Pose() for mp in mk], np.float64).reshape(-1, 3),
+                kf_bad=np.array([1 if mp.IsBad() else 0 for mp in mk], np.uint8),
+                local_kf_centre=np.array([centre(k) for k in local_keyframes], np.float64).reshape(-1, 3))
+
+
 class Tracker:
     """Tracking's per-frame flow (src/Tracking.cpp:199-256) on top of track_frame, with the reference's side effects: the new
     Frame gets the pose, the features SearchLocalPoints creates (px, level, bearing, map point, mbInitial) and the refined
@@ -259,6 +289,16 @@ class Tracker:
                         keyframes, map_points, mask=img_mask, cur_frame=cur_frame)
         self.last_result = r
         return apply_tracked_frame(self.cam, image, r, map_points, img_mask)
+
+    def keyframe_params(self) -> KeyframeParams:
+        """Tracking's thresholds of NeedKeyframe: KeyFrame.min_rot / min_trans (src/Tracking.cpp:26-27), the constants of :354-378."""
+        return KeyframeParams(min_rot=float(Config.Get("KeyFrame.min_rot")), min_trans=float(Config.Get("KeyFrame.min_trans")))
+
+    def NeedKeyframe(self, cur, last_kf, local_keyframes, params=None) -> dict:
+        """Tracking::NeedKeyframe (src/Tracking.cpp:347-410) for the tracked frame `cur` against the last keyframe and
+        mvpLocalKeyFrames, through dsdtm_need_keyframe. Returns the verdict as a dict (need, reason, rule_mask, ...: the fields of
+        dsdtm_keyframe_verdict). Reads the objects only: TrackFrame's results are untouched."""
+        return capi.need_keyframe(self.ctx, self.cam, params or self.keyframe_params(), keyframe_desc(cur, last_kf, local_keyframes))
 
 
 class MultiTracker:
@@ -321,3 +361,11 @@ class MultiTracker:
             out.append(apply_tracked_frame(self.cam, images[i], r, map_points[i], img_masks[i]))
         self.last_results = rs
         return out
+
+    def NeedKeyframes(self, curs, last_kfs, local_keyframes, params=None) -> list:
+        """Tracker.NeedKeyframe for the n sequences of a step in ONE dsdtm_need_keyframes call (lists of n: the frames TrackFrames
+        returned, each sequence's last keyframe and its mvpLocalKeyFrames). Returns n verdict dicts."""
+        if not (len(curs) == len(last_kfs) == len(local_keyframes)):
+            raise ValueError(f"{len(curs)} frames, {len(last_kfs)} last keyframes, {len(local_keyframes)} local keyframe lists")
+        descs = [keyframe_desc(c, k, lk) for c, k, lk in zip(curs, last_kfs, local_keyframes)]
+        return capi.need_keyframes(self.ctx, self.cam, params or self.t.keyframe_params(), descs)
