@@ -178,11 +178,42 @@ static void copy_rows(void* dst, size_t dst_stride, const void* src, size_t src_
     for (size_t y = 0; y < rows; ++y) memcpy((uint8_t*)dst + y * dst_stride, (const uint8_t*)src + y * src_stride, row_bytes);
 }
 
-// the level table of a batch descriptor whose pyramids are packed
-static void fill_levels(dsdtm_batch_desc& b, const PackedPyr& pl) {
+// the level table of a batch / image descriptor whose pyramids are packed
+template <class Desc>
+static void fill_levels(Desc& b, const PackedPyr& pl) {
     b.levels = pl.levels;
     for (int l = 0; l < pl.levels; ++l) { b.width[l] = pl.w[l]; b.height[l] = pl.h[l]; b.stride[l] = pl.w[l]; b.level_offset[l] = pl.off[l]; }
 }
+// ... and the first `levels` levels of a packed pyramid as the kernels take them
+static void fill_levels(LevelGeom* lv, const PackedPyr& pl, int levels) {
+    for (int l = 0; l < levels; ++l) { lv[l].w = pl.w[l]; lv[l].h = pl.h[l]; lv[l].stride = pl.w[l]; lv[l].off = (uint32_t)pl.off[l]; }
+}
+static bool same_geometry(const PackedPyr& a, const PackedPyr& b) {
+    return a.levels == b.levels && !memcmp(a.w, b.w, sizeof(int) * a.levels) && !memcmp(a.h, b.h, sizeof(int) * a.levels);
+}
+
+// Level l of a caller's level table lies inside `limit` bytes: it has pixels, its rows are no shorter than they are wide and its
+// last row ends inside. lv (may be NULL: the check alone): the level as the kernels take it.
+static bool level_fits(int l, const int* width, const int* height, const int* stride, const size_t* level_offset, size_t limit, LevelGeom* lv) {
+    if (width[l] <= 0 || height[l] <= 0 || stride[l] < width[l] || level_offset[l] + (size_t)stride[l] * height[l] > limit) return false;
+    if (lv) { lv[l].w = width[l]; lv[l].h = height[l]; lv[l].stride = stride[l]; lv[l].off = (uint32_t)level_offset[l]; }
+    return true;
+}
+// ... for a whole table; the first level that does not fit is named in the message. who: the entry's prefix; inside: the limit in its words.
+static int check_levels(dsdtm_ctx* ctx, int levels, const int* width, const int* height, const int* stride, const size_t* level_offset,
+                        size_t limit, const char* who, const char* inside, LevelGeom* lv) {
+    for (int l = 0; l < levels; ++l)
+        if (!level_fits(l, width, height, stride, level_offset, limit, lv)) {
+            set_err(ctx, "%slevel %d does not fit inside %s", who, l, inside); return DSDTM_ERR_INVALID;
+        }
+    return DSDTM_OK;
+}
+
+// The layout of a staging block: a column starts where the one before it ended, rounded up to its alignment (an empty column takes no room)
+struct StageLayout {
+    size_t off = 0;
+    size_t take(size_t bytes, size_t align = 256) { const size_t o = off; off = align_up(off + bytes, align); return o; }
+};
 
 // behind a timeout word of `stream` (which has drained): a pair that was stopped may have left its counter word behind
 static void clear_stream_counters(dsdtm_ctx* ctx, hipStream_t stream) {
@@ -389,6 +420,14 @@ static int ensure_stage(dsdtm_ctx* ctx, size_t bytes) {
     return DSDTM_OK;
 }
 
+// The pinned staging block as the device addresses it (asked for at every call, as before: the block may have been regrown)
+static int pinned_device_ptr(dsdtm_ctx* ctx, uint8_t** p) {
+    void* hd = nullptr;
+    HIP_TRY(ctx, hipHostGetDevicePointer(&hd, ctx->h_pinned, 0));
+    *p = (uint8_t*)hd;
+    return DSDTM_OK;
+}
+
 extern "C" int dsdtm_reserve(dsdtm_ctx* ctx, size_t workspace_bytes) {
     if (!ctx) return DSDTM_ERR_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -529,14 +568,7 @@ static int launch_batch(dsdtm_ctx* ctx, const dsdtm_batch_desc* b, const dsdtm_c
     }
     SAKernelArgs a;
     memset(&a, 0, sizeof a);
-    for (int l = 0; l < b->levels; ++l) {
-        const size_t end = b->level_offset[l] + (size_t)b->stride[l] * b->height[l];
-        if (b->width[l] <= 0 || b->height[l] <= 0 || b->stride[l] < b->width[l] || end > b->pyr_pitch) {
-            set_err(ctx, "level %d does not fit inside pyr_pitch", l); return DSDTM_ERR_INVALID;
-        }
-        a.lv[l].w = b->width[l]; a.lv[l].h = b->height[l]; a.lv[l].stride = b->stride[l];
-        a.lv[l].off = (uint32_t)b->level_offset[l];
-    }
+    if (int rc = check_levels(ctx, b->levels, b->width, b->height, b->stride, b->level_offset, b->pyr_pitch, "", "pyr_pitch", a.lv)) return rc;
     a.ref_pyr = b->ref_pyr; a.cur_pyr = b->cur_pyr; a.px_xy = b->px_xy; a.bearing = b->bearing;
     a.p_world = b->p_world; a.initial = b->initial; a.n_features = b->n_features;
     a.T_ref_w = b->T_ref_w; a.T_cur_w = b->T_cur_w; a.n_tracked = b->n_tracked; a.stats = b->stats;
@@ -773,6 +805,49 @@ extern "C" void dsdtm_shard_range(int n_pairs, int n_shards, int shard, int* lo,
     if (hi) *hi = h;
 }
 
+// The context's device staging alone, grown to `bytes` (never shrunk; what the context's stream still does with the old block is waited for)
+static int ensure_device_stage(dsdtm_ctx* ctx, size_t bytes) {
+    if (bytes <= ctx->d_cap) return DSDTM_OK;
+    if (ctx->d_stage) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_stage); }
+    ctx->d_stage = nullptr; ctx->d_cap = 0;
+    HIP_TRY(ctx, hipMalloc(&ctx->d_stage, bytes));
+    ctx->d_cap = bytes;
+    return DSDTM_OK;
+}
+
+// Where the columns of a staged batch start in its block (pair 0 of each; nf / st: only where has_nf / has_st)
+struct BatchColumns { size_t ref, cur, px, be, pw, in, nf, tr, tc, nt, st; bool has_nf, has_st; };
+// the columns of a shard of n pairs (n_ref reference pyramids; cur_in_ref: the current pyramids are the reference ones, shifted by one)
+static BatchColumns plan_batch_columns(StageLayout& L, size_t n, size_t n_ref, bool cur_in_ref, size_t pit, size_t nf, bool has_nf, bool has_st) {
+    BatchColumns c;
+    c.ref = L.take(n_ref * pit); c.cur = cur_in_ref ? c.ref + pit : L.take(n * pit);
+    c.px = L.take(n * nf * 8); c.be = L.take(n * nf * 24); c.pw = L.take(n * nf * 24); c.in = L.take(n * nf);
+    c.nf = L.take(has_nf ? n * 4 : 0); c.tr = L.take(n * 96); c.tc = L.take(n * 96); c.nt = L.take(n * 4);
+    c.st = L.take(has_st ? n * sizeof(dsdtm_align_stats) : 0);
+    c.has_nf = has_nf; c.has_st = has_st;
+    return c;
+}
+// b's pair count and columns: pairs [p0, p1) of the block at d (levels, pitch and max_features stay as they are)
+static void bind_batch_columns(dsdtm_batch_desc& b, uint8_t* d, const BatchColumns& c, size_t pit, size_t nf, size_t p0, size_t p1) {
+    b.n_pairs = (int)(p1 - p0);
+    b.ref_pyr = d + c.ref + p0 * pit; b.cur_pyr = d + c.cur + p0 * pit;
+    b.px_xy = (const float*)(d + c.px + p0 * nf * 8); b.bearing = (const double*)(d + c.be + p0 * nf * 24);
+    b.p_world = (const double*)(d + c.pw + p0 * nf * 24); b.initial = d + c.in + p0 * nf;
+    b.n_features = c.has_nf ? (const int32_t*)(d + c.nf + p0 * 4) : nullptr;
+    b.T_ref_w = (const double*)(d + c.tr + p0 * 96); b.T_cur_w = (double*)(d + c.tc + p0 * 96);
+    b.n_tracked = (int32_t*)(d + c.nt + p0 * 4);
+    b.stats = c.has_st ? (dsdtm_align_stats*)(d + c.st + p0 * sizeof(dsdtm_align_stats)) : nullptr;
+}
+// the three result downloads of pairs [p0, p1) of the block into the caller's arrays, whose pair `first` is the block's pair 0
+static int enqueue_result_downloads(dsdtm_ctx* ctx, double* T_cur_w, int32_t* n_tracked, dsdtm_align_stats* stats, size_t first, const uint8_t* d,
+                                    const BatchColumns& c, size_t p0, size_t p1, hipStream_t st) {
+    const size_t g0 = first + p0, np = p1 - p0;
+    HIP_TRY(ctx, hipMemcpyAsync(T_cur_w + g0 * 12, d + c.tc + p0 * 96, np * 96, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(n_tracked + g0, d + c.nt + p0 * 4, np * 4, hipMemcpyDeviceToHost, st));
+    if (stats) HIP_TRY(ctx, hipMemcpyAsync(stats + g0, d + c.st + p0 * sizeof(dsdtm_align_stats), np * sizeof(dsdtm_align_stats), hipMemcpyDeviceToHost, st));
+    return DSDTM_OK;
+}
+
 // One shard: pairs [lo, hi) of the host batch on `ctx` (its device, its stream). Device scratch comes from the
 // context's staging buffer (device side only: the caller's arrays may be pageable, the copies are then staged by
 // the runtime; pinned arrays are copied directly).
@@ -782,46 +857,27 @@ static int sharded_issue(dsdtm_ctx* ctx, const dsdtm_batch_desc* hb, const dsdtm
     if (n <= 0) return DSDTM_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t nf = (size_t)hb->max_features, pit = hb->pyr_pitch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_ref = take(n * pit), o_cur = take(n * pit), o_px = take(n * nf * 8), o_be = take(n * nf * 24),
-                 o_pw = take(n * nf * 24), o_in = take(n * nf), o_nf = take(hb->n_features ? n * 4 : 0),
-                 o_tr = take(n * 96), o_tc = take(n * 96), o_nt = take(n * 4),
-                 o_st = take(hb->stats ? n * sizeof(dsdtm_align_stats) : 0);
-    if (off > ctx->d_cap) {
-        if (ctx->d_stage) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_stage); }
-        ctx->d_stage = nullptr; ctx->d_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_stage, off));
-        ctx->d_cap = off;
-    }
+    StageLayout lay;
+    const BatchColumns c = plan_batch_columns(lay, (size_t)n, (size_t)n, false, pit, nf, hb->n_features != nullptr, hb->stats != nullptr);
+    if (int rc = ensure_device_stage(ctx, lay.off)) return rc;
     uint8_t* d = (uint8_t*)ctx->d_stage;
     hipStream_t st = ctx->stream;
     auto up = [&](size_t o, const void* src, size_t bytes) {
         return bytes ? hipMemcpyAsync(d + o, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
     };
-    HIP_TRY(ctx, up(o_ref, hb->ref_pyr + (size_t)lo * pit, n * pit));
-    HIP_TRY(ctx, up(o_cur, hb->cur_pyr + (size_t)lo * pit, n * pit));
-    HIP_TRY(ctx, up(o_px, hb->px_xy + (size_t)lo * nf * 2, n * nf * 8));
-    HIP_TRY(ctx, up(o_be, hb->bearing + (size_t)lo * nf * 3, n * nf * 24));
-    HIP_TRY(ctx, up(o_pw, hb->p_world + (size_t)lo * nf * 3, n * nf * 24));
-    HIP_TRY(ctx, up(o_in, hb->initial + (size_t)lo * nf, n * nf));
-    if (hb->n_features) HIP_TRY(ctx, up(o_nf, hb->n_features + lo, n * 4));
-    HIP_TRY(ctx, up(o_tr, hb->T_ref_w + (size_t)lo * 12, n * 96));
-    HIP_TRY(ctx, up(o_tc, hb->T_cur_w + (size_t)lo * 12, n * 96));
+    HIP_TRY(ctx, up(c.ref, hb->ref_pyr + (size_t)lo * pit, n * pit));
+    HIP_TRY(ctx, up(c.cur, hb->cur_pyr + (size_t)lo * pit, n * pit));
+    HIP_TRY(ctx, up(c.px, hb->px_xy + (size_t)lo * nf * 2, n * nf * 8));
+    HIP_TRY(ctx, up(c.be, hb->bearing + (size_t)lo * nf * 3, n * nf * 24));
+    HIP_TRY(ctx, up(c.pw, hb->p_world + (size_t)lo * nf * 3, n * nf * 24));
+    HIP_TRY(ctx, up(c.in, hb->initial + (size_t)lo * nf, n * nf));
+    if (hb->n_features) HIP_TRY(ctx, up(c.nf, hb->n_features + lo, n * 4));
+    HIP_TRY(ctx, up(c.tr, hb->T_ref_w + (size_t)lo * 12, n * 96));
+    HIP_TRY(ctx, up(c.tc, hb->T_cur_w + (size_t)lo * 12, n * 96));
     dsdtm_batch_desc b = *hb;
-    b.n_pairs = n;
-    b.ref_pyr = d + o_ref; b.cur_pyr = d + o_cur;
-    b.px_xy = (const float*)(d + o_px); b.bearing = (const double*)(d + o_be); b.p_world = (const double*)(d + o_pw);
-    b.initial = d + o_in; b.n_features = hb->n_features ? (const int32_t*)(d + o_nf) : nullptr;
-    b.T_ref_w = (const double*)(d + o_tr); b.T_cur_w = (double*)(d + o_tc);
-    b.n_tracked = (int32_t*)(d + o_nt); b.stats = hb->stats ? (dsdtm_align_stats*)(d + o_st) : nullptr;
+    bind_batch_columns(b, d, c, pit, nf, 0, (size_t)n);
     if (int rc = dsdtm_sparse_align_batch_device(ctx, &b, cam, prm, st)) return rc;
-    auto download = [&]() -> int {
-        HIP_TRY(ctx, hipMemcpyAsync(hb->T_cur_w + (size_t)lo * 12, d + o_tc, n * 96, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(hb->n_tracked + lo, d + o_nt, n * 4, hipMemcpyDeviceToHost, st));
-        if (hb->stats) HIP_TRY(ctx, hipMemcpyAsync(hb->stats + lo, d + o_st, n * sizeof(dsdtm_align_stats), hipMemcpyDeviceToHost, st));
-        return DSDTM_OK;
-    };
+    auto download = [&]() { return enqueue_result_downloads(ctx, hb->T_cur_w, hb->n_tracked, hb->stats, (size_t)lo, d, c, 0, (size_t)n, st); };
     // the downloads overlap nothing when queued before the check, but the check may re-seed and re-run a multi-CU launch whose
     // wait for a partner workgroup ran out (recover_settle): the host arrays then hold the aborted launch's poses and are
     // fetched again
@@ -832,6 +888,47 @@ static int sharded_issue(dsdtm_ctx* ctx, const dsdtm_batch_desc* hb, const dsdtm
         if (int rc = download()) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(st));
     }
+    return DSDTM_OK;
+}
+
+// The shard list of the two multi-context entries: no NULL context, no context twice (a context's stream and staging serve one shard)
+static bool has_null_context(dsdtm_ctx* const* ctx, int n_ctx) {
+    for (int g = 0; g < n_ctx; ++g) if (!ctx[g]) return true;
+    return false;
+}
+static int check_distinct_contexts(dsdtm_ctx* const* ctx, int n_ctx, const char* who) {
+    for (int g = 0; g < n_ctx; ++g)
+        for (int h = g + 1; h < n_ctx; ++h)
+            if (ctx[g] == ctx[h]) { set_err(ctx[0], "%s: a context appears twice (one context per shard)", who); return DSDTM_ERR_INVALID; }
+    return DSDTM_OK;
+}
+// fn(g, lo, hi) for the shard of every context (dsdtm_shard_range over n_pairs): shards 1.. on a host thread each, shard 0 on the
+// calling thread. Returns the first code that is not DSDTM_OK, in shard order. A shard whose thread cannot be started fails with
+// DSDTM_ERR_NOMEM; no further shard is started then and shard 0 is not run.
+template <class Fn>
+static int run_shards(dsdtm_ctx* const* ctx, int n_ctx, int n_pairs, const char* who, Fn fn) {
+    std::vector<int> rc(n_ctx, DSDTM_OK);
+    std::vector<std::thread> th;
+    bool spawn_failed = false;
+    try { th.reserve((size_t)n_ctx); } catch (...) { set_err(ctx[0], "%s: out of memory", who); return DSDTM_ERR_NOMEM; }
+    for (int g = 1; g < n_ctx && !spawn_failed; ++g) {
+        int lo, hi;
+        dsdtm_shard_range(n_pairs, n_ctx, g, &lo, &hi);
+        try {
+            th.emplace_back([=, &rc]() { rc[g] = fn(g, lo, hi); });
+        } catch (...) {           // no exception crosses the C boundary: the shards already started are joined below
+            spawn_failed = true;
+            rc[g] = DSDTM_ERR_NOMEM;
+            set_err(ctx[g], "%s: could not start the host thread of shard %d", who, g);
+        }
+    }
+    if (!spawn_failed) {
+        int lo, hi;
+        dsdtm_shard_range(n_pairs, n_ctx, 0, &lo, &hi);
+        rc[0] = fn(0, lo, hi);                                  // the calling thread takes the first shard
+    }
+    for (auto& t : th) t.join();
+    for (int g = 0; g < n_ctx; ++g) if (rc[g] != DSDTM_OK) return rc[g];
     return DSDTM_OK;
 }
 
@@ -850,14 +947,12 @@ static int sharded_one(dsdtm_ctx* ctx, const dsdtm_batch_desc* hb, const dsdtm_c
 extern "C" int dsdtm_sparse_align_batch_sharded(dsdtm_ctx* const* ctx, int n_ctx, const dsdtm_batch_desc* hb,
                                                 const dsdtm_camera* cam, const dsdtm_align_params* prm) {
     if (!ctx || n_ctx <= 0 || !hb || !cam || !prm) return DSDTM_ERR_INVALID;
-    for (int g = 0; g < n_ctx; ++g) if (!ctx[g]) return DSDTM_ERR_INVALID;
+    if (has_null_context(ctx, n_ctx)) return DSDTM_ERR_INVALID;
     if (hb->n_pairs < 0 || !hb->ref_pyr || !hb->cur_pyr || !hb->T_ref_w || !hb->T_cur_w || !hb->n_tracked ||
         (hb->max_features > 0 && (!hb->px_xy || !hb->bearing || !hb->p_world || !hb->initial))) {
         set_err(ctx[0], "sharded batch: NULL host pointers"); return DSDTM_ERR_INVALID;
     }
-    for (int g = 0; g < n_ctx; ++g)
-        for (int h = g + 1; h < n_ctx; ++h)
-            if (ctx[g] == ctx[h]) { set_err(ctx[0], "sharded batch: a context appears twice (one context per shard)"); return DSDTM_ERR_INVALID; }
+    if (int rc = check_distinct_contexts(ctx, n_ctx, "sharded batch")) return rc;
     // the descriptor is checked BEFORE any shard sizes its staging from it or a thread is started
     if (hb->max_features < 0 || hb->max_features > 32767 || hb->levels <= 0 || hb->levels > DSDTM_MAX_LEVELS ||
         hb->pyr_pitch == 0 || (hb->pyr_pitch & 3) || hb->pyr_pitch > 0xffffffffull) {
@@ -866,35 +961,8 @@ extern "C" int dsdtm_sparse_align_batch_sharded(dsdtm_ctx* const* ctx, int n_ctx
         return DSDTM_ERR_INVALID;
     }
     if (int rc0 = validate_params(ctx[0], prm, hb->levels)) return rc0;
-    for (int l = 0; l < hb->levels; ++l) {
-        const size_t end = hb->level_offset[l] + (size_t)hb->stride[l] * hb->height[l];
-        if (hb->width[l] <= 0 || hb->height[l] <= 0 || hb->stride[l] < hb->width[l] || end > hb->pyr_pitch) {
-            set_err(ctx[0], "sharded batch: level %d does not fit inside pyr_pitch", l); return DSDTM_ERR_INVALID;
-        }
-    }
-    std::vector<int> rc(n_ctx, DSDTM_OK);
-    std::vector<std::thread> th;
-    bool spawn_failed = false;
-    try { th.reserve((size_t)n_ctx); } catch (...) { set_err(ctx[0], "sharded batch: out of memory"); return DSDTM_ERR_NOMEM; }
-    for (int g = 1; g < n_ctx && !spawn_failed; ++g) {
-        int lo, hi;
-        dsdtm_shard_range(hb->n_pairs, n_ctx, g, &lo, &hi);
-        try {
-            th.emplace_back([=, &rc]() { rc[g] = sharded_one(ctx[g], hb, cam, prm, lo, hi); });
-        } catch (...) {           // no exception crosses the C boundary: the shards already started are joined below
-            spawn_failed = true;
-            rc[g] = DSDTM_ERR_NOMEM;
-            set_err(ctx[g], "sharded batch: could not start the host thread of shard %d", g);
-        }
-    }
-    if (!spawn_failed) {
-        int lo, hi;
-        dsdtm_shard_range(hb->n_pairs, n_ctx, 0, &lo, &hi);
-        rc[0] = sharded_one(ctx[0], hb, cam, prm, lo, hi);      // the calling thread takes the first shard
-    }
-    for (auto& t : th) t.join();
-    for (int g = 0; g < n_ctx; ++g) if (rc[g] != DSDTM_OK) return rc[g];
-    return DSDTM_OK;
+    if (int rc = check_levels(ctx[0], hb->levels, hb->width, hb->height, hb->stride, hb->level_offset, hb->pyr_pitch, "sharded batch: ", "pyr_pitch", nullptr)) return rc;
+    return run_shards(ctx, n_ctx, hb->n_pairs, "sharded batch", [=](int g, int lo, int hi) { return sharded_one(ctx[g], hb, cam, prm, lo, hi); });
 }
 
 // ---- the batch STREAMED from host memory: level 0 only, chunked, copy overlapped with compute ---------------
@@ -915,18 +983,9 @@ static int streamed_issue(dsdtm_ctx* ctx, const dsdtm_stream_desc* s, const dsdt
     plan_image_pyramid(s->width, s->height, s->levels, &pl, st);
     const size_t pit = align_up(pl.bytes, 256), img = (size_t)s->width * s->height, nf = (size_t)s->max_features;
     const int n_frames = chained ? n + 1 : n;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t v = off; off = align_up(off + bytes, 256); return v; };
-    const size_t o_ref = take((size_t)n_frames * pit), o_cur = chained ? o_ref + pit : take((size_t)n * pit),
-                 o_px = take(n * nf * 8), o_be = take(n * nf * 24), o_pw = take(n * nf * 24), o_in = take(n * nf),
-                 o_nf = take(s->n_features ? (size_t)n * 4 : 0), o_tr = take((size_t)n * 96), o_tc = take((size_t)n * 96),
-                 o_nt = take((size_t)n * 4), o_st = take(s->stats ? n * sizeof(dsdtm_align_stats) : 0);
-    if (off > ctx->d_cap) {
-        if (ctx->d_stage) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_stage); }
-        ctx->d_stage = nullptr; ctx->d_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_stage, off));
-        ctx->d_cap = off;
-    }
+    StageLayout lay;
+    const BatchColumns c = plan_batch_columns(lay, (size_t)n, (size_t)n_frames, chained, pit, nf, s->n_features != nullptr, s->stats != nullptr);
+    if (int rc = ensure_device_stage(ctx, lay.off)) return rc;
     uint8_t* d = (uint8_t*)ctx->d_stage;
     for (int i = 0; i < 2; ++i)
         if (!ctx->copy_stream[i]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream[i], hipStreamNonBlocking));
@@ -969,42 +1028,31 @@ static int streamed_issue(dsdtm_ctx* ctx, const dsdtm_stream_desc* s, const dsdt
         hipStream_t cs = ctx->copy_stream[j & 1];
         // frames that arrive with this chunk — chained: the `cur` frames of its pairs (+ frame 0 with the first chunk)
         const int f0 = chained ? (j == 0 ? 0 : p0 + 1) : p0, f1 = chained ? p1 + 1 : p1;
-        HIP_TRY(ctx, up_images(cs, ref_h, o_ref, f0, f1));
-        if (!chained) HIP_TRY(ctx, up_images(cs, cur_h, o_cur, p0, p1));
+        HIP_TRY(ctx, up_images(cs, ref_h, c.ref, f0, f1));
+        if (!chained) HIP_TRY(ctx, up_images(cs, cur_h, c.cur, p0, p1));
         const size_t g0 = (size_t)(lo + p0);                                   // first pair of the chunk in the host arrays
-        HIP_TRY(ctx, up(cs, o_px + p0 * nf * 8, s->px_xy + g0 * nf * 2, np * nf * 8));
-        HIP_TRY(ctx, up(cs, o_be + p0 * nf * 24, s->bearing + g0 * nf * 3, np * nf * 24));
-        HIP_TRY(ctx, up(cs, o_pw + p0 * nf * 24, s->p_world + g0 * nf * 3, np * nf * 24));
-        HIP_TRY(ctx, up(cs, o_in + p0 * nf, s->initial + g0 * nf, np * nf));
-        if (s->n_features) HIP_TRY(ctx, up(cs, o_nf + (size_t)p0 * 4, s->n_features + g0, np * 4));
-        HIP_TRY(ctx, up(cs, o_tr + (size_t)p0 * 96, s->T_ref_w + g0 * 12, np * 96));
-        HIP_TRY(ctx, up(cs, o_tc + (size_t)p0 * 96, s->T_cur_w + g0 * 12, np * 96));
+        HIP_TRY(ctx, up(cs, c.px + p0 * nf * 8, s->px_xy + g0 * nf * 2, np * nf * 8));
+        HIP_TRY(ctx, up(cs, c.be + p0 * nf * 24, s->bearing + g0 * nf * 3, np * nf * 24));
+        HIP_TRY(ctx, up(cs, c.pw + p0 * nf * 24, s->p_world + g0 * nf * 3, np * nf * 24));
+        HIP_TRY(ctx, up(cs, c.in + p0 * nf, s->initial + g0 * nf, np * nf));
+        if (s->n_features) HIP_TRY(ctx, up(cs, c.nf + (size_t)p0 * 4, s->n_features + g0, np * 4));
+        HIP_TRY(ctx, up(cs, c.tr + (size_t)p0 * 96, s->T_ref_w + g0 * 12, np * 96));
+        HIP_TRY(ctx, up(cs, c.tc + (size_t)p0 * 96, s->T_cur_w + g0 * 12, np * 96));
         HIP_TRY(ctx, hipEventRecord(ctx->copy_events[j], cs));
         HIP_TRY(ctx, hipStreamWaitEvent(comp, ctx->copy_events[j], 0));
         // Frame::ComputeImagePyramid (src/Frame.cpp:74-81) for the frames that just arrived, on the device
-        if (int rc = dsdtm_pyrdown_batch_device(ctx, d + o_ref + (size_t)f0 * pit, pit, f1 - f0, s->levels, pl.w, pl.h, st, pl.off, comp)) return rc;
+        if (int rc = dsdtm_pyrdown_batch_device(ctx, d + c.ref + (size_t)f0 * pit, pit, f1 - f0, s->levels, pl.w, pl.h, st, pl.off, comp)) return rc;
         if (!chained)
-            if (int rc = dsdtm_pyrdown_batch_device(ctx, d + o_cur + (size_t)p0 * pit, pit, p1 - p0, s->levels, pl.w, pl.h, st, pl.off, comp)) return rc;
-        b.n_pairs = p1 - p0;
-        b.ref_pyr = d + o_ref + (size_t)p0 * pit; b.cur_pyr = d + o_cur + (size_t)p0 * pit;
-        b.px_xy = (const float*)(d + o_px + p0 * nf * 8); b.bearing = (const double*)(d + o_be + p0 * nf * 24);
-        b.p_world = (const double*)(d + o_pw + p0 * nf * 24); b.initial = d + o_in + p0 * nf;
-        b.n_features = s->n_features ? (const int32_t*)(d + o_nf + (size_t)p0 * 4) : nullptr;
-        b.T_ref_w = (const double*)(d + o_tr + (size_t)p0 * 96); b.T_cur_w = (double*)(d + o_tc + (size_t)p0 * 96);
-        b.n_tracked = (int32_t*)(d + o_nt + (size_t)p0 * 4);
-        b.stats = s->stats ? (dsdtm_align_stats*)(d + o_st + p0 * sizeof(dsdtm_align_stats)) : nullptr;
+            if (int rc = dsdtm_pyrdown_batch_device(ctx, d + c.cur + (size_t)p0 * pit, pit, p1 - p0, s->levels, pl.w, pl.h, st, pl.off, comp)) return rc;
+        bind_batch_columns(b, d, c, pit, nf, (size_t)p0, (size_t)p1);
         if (int rc = dsdtm_sparse_align_batch_device(ctx, &b, cam, prm, comp)) return rc;
         // (multi-CU shapes: results are final after the check below; a chunk's download is repeated there if it was re-run)
-        HIP_TRY(ctx, hipMemcpyAsync(s->T_cur_w + g0 * 12, d + o_tc + (size_t)p0 * 96, np * 96, hipMemcpyDeviceToHost, comp));
-        HIP_TRY(ctx, hipMemcpyAsync(s->n_tracked + g0, d + o_nt + (size_t)p0 * 4, np * 4, hipMemcpyDeviceToHost, comp));
-        if (s->stats) HIP_TRY(ctx, hipMemcpyAsync(s->stats + g0, d + o_st + p0 * sizeof(dsdtm_align_stats), np * sizeof(dsdtm_align_stats), hipMemcpyDeviceToHost, comp));
+        if (int rc = enqueue_result_downloads(ctx, s->T_cur_w, s->n_tracked, s->stats, (size_t)lo, d, c, (size_t)p0, (size_t)p1, comp)) return rc;
     }
     const unsigned long long rerun0 = ctx->recovered;
     if (int rc = dsdtm_sparse_align_check(ctx, comp)) return rc;
     if (ctx->recovered != rerun0) {          // a chunk was re-run on the one-CU kernels: fetch everything again
-        HIP_TRY(ctx, hipMemcpyAsync(s->T_cur_w + (size_t)lo * 12, d + o_tc, (size_t)n * 96, hipMemcpyDeviceToHost, comp));
-        HIP_TRY(ctx, hipMemcpyAsync(s->n_tracked + lo, d + o_nt, (size_t)n * 4, hipMemcpyDeviceToHost, comp));
-        if (s->stats) HIP_TRY(ctx, hipMemcpyAsync(s->stats + lo, d + o_st, n * sizeof(dsdtm_align_stats), hipMemcpyDeviceToHost, comp));
+        if (int rc = enqueue_result_downloads(ctx, s->T_cur_w, s->n_tracked, s->stats, (size_t)lo, d, c, 0, (size_t)n, comp)) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(comp));
     }
     return DSDTM_OK;
@@ -1026,10 +1074,8 @@ static int streamed_one(dsdtm_ctx* ctx, const dsdtm_stream_desc* s, const dsdtm_
 extern "C" int dsdtm_sparse_align_batch_streamed(dsdtm_ctx* const* ctx, int n_ctx, const dsdtm_stream_desc* s, int chunk_pairs,
                                                  const dsdtm_camera* cam, const dsdtm_align_params* prm) {
     if (!ctx || n_ctx <= 0 || !s || !cam || !prm) return DSDTM_ERR_INVALID;
-    for (int g = 0; g < n_ctx; ++g) if (!ctx[g]) return DSDTM_ERR_INVALID;
-    for (int g = 0; g < n_ctx; ++g)
-        for (int k = g + 1; k < n_ctx; ++k)
-            if (ctx[g] == ctx[k]) { set_err(ctx[0], "streamed batch: a context appears twice (one context per shard)"); return DSDTM_ERR_INVALID; }
+    if (has_null_context(ctx, n_ctx)) return DSDTM_ERR_INVALID;
+    if (int rc = check_distinct_contexts(ctx, n_ctx, "streamed batch")) return rc;
     if (s->n_pairs < 0 || !s->ref_image || !s->T_ref_w || !s->T_cur_w || !s->n_tracked ||
         (s->max_features > 0 && (!s->px_xy || !s->bearing || !s->p_world || !s->initial))) {
         set_err(ctx[0], "streamed batch: NULL host pointers"); return DSDTM_ERR_INVALID;
@@ -1040,29 +1086,7 @@ extern "C" int dsdtm_sparse_align_batch_streamed(dsdtm_ctx* const* ctx, int n_ct
     }
     if (int rc0 = validate_params(ctx[0], prm, s->levels)) return rc0;
     const int chunk = chunk_pairs > 0 ? chunk_pairs : 128;
-    std::vector<int> rc(n_ctx, DSDTM_OK);
-    std::vector<std::thread> th;
-    bool spawn_failed = false;
-    try { th.reserve((size_t)n_ctx); } catch (...) { set_err(ctx[0], "streamed batch: out of memory"); return DSDTM_ERR_NOMEM; }
-    for (int g = 1; g < n_ctx && !spawn_failed; ++g) {
-        int lo, hi;
-        dsdtm_shard_range(s->n_pairs, n_ctx, g, &lo, &hi);
-        try {
-            th.emplace_back([=, &rc]() { rc[g] = streamed_one(ctx[g], s, cam, prm, chunk, lo, hi); });
-        } catch (...) {
-            spawn_failed = true;
-            rc[g] = DSDTM_ERR_NOMEM;
-            set_err(ctx[g], "streamed batch: could not start the host thread of shard %d", g);
-        }
-    }
-    if (!spawn_failed) {
-        int lo, hi;
-        dsdtm_shard_range(s->n_pairs, n_ctx, 0, &lo, &hi);
-        rc[0] = streamed_one(ctx[0], s, cam, prm, chunk, lo, hi);
-    }
-    for (auto& t : th) t.join();
-    for (int g = 0; g < n_ctx; ++g) if (rc[g] != DSDTM_OK) return rc[g];
-    return DSDTM_OK;
+    return run_shards(ctx, n_ctx, s->n_pairs, "streamed batch", [=](int g, int lo, int hi) { return streamed_one(ctx[g], s, cam, prm, chunk, lo, hi); });
 }
 
 // ---- host staging helpers ---------------------------------------------------------------
@@ -1091,6 +1115,14 @@ static void pack_pyramid(const dsdtm_pyramid* p, const PackedPyr& pl, uint8_t* d
     }
 }
 
+// the two pyramids of one alignment have the same geometry (the message says which level does not)
+static int check_ref_cur_geometry(dsdtm_ctx* ctx, const PackedPyr& pr, const PackedPyr& pc) {
+    if (pr.levels != pc.levels) { set_err(ctx, "ref/cur pyramids differ in level count"); return DSDTM_ERR_INVALID; }
+    for (int l = 0; l < pr.levels; ++l)
+        if (pr.w[l] != pc.w[l] || pr.h[l] != pc.h[l]) { set_err(ctx, "ref/cur level %d differ in size", l); return DSDTM_ERR_INVALID; }
+    return DSDTM_OK;
+}
+
 // One alignment on the context's stream. The pyramids are either packed into the staging buffer
 // together with the features (ref/cur given, dev_ref/dev_cur null) or already on the device.
 static int sparse_align_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyramid* ref, const dsdtm_pyramid* cur,
@@ -1109,19 +1141,15 @@ static int sparse_align_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
     const bool staged_pyr = dev_ref == nullptr;
     const size_t nf = (size_t)n_features;
     const size_t pitch = staged_pyr ? align_up(pl.bytes, 256) : dev_pitch;
-    size_t o = 0;
-    const size_t o_ref = o; if (staged_pyr) o += pitch;
-    const size_t o_cur = o; if (staged_pyr) o += pitch;
-    const size_t o_bear = o; o += align_up(nf * 24, 256);
-    const size_t o_pw = o; o += align_up(nf * 24, 256);
-    const size_t o_tr = o; o += 256;
-    const size_t o_px = o; o += align_up(nf * 8, 256);
-    const size_t o_ini = o; o += align_up(nf, 256);
-    const size_t in_bytes = o;
-    const size_t o_tc = o; o += 256;          // in (seed) and out
-    const size_t o_nt = o; o += 256;
-    const size_t o_st = o; o += align_up(sizeof(dsdtm_align_stats), 256);
-    const size_t total = o;
+    // (its own column order: what goes up first, then the seed, which is read and written, then what only comes back; the poses
+    // and the count take a 256-byte cell each)
+    StageLayout lay;
+    const size_t o_ref = lay.take(staged_pyr ? pitch : 0), o_cur = lay.take(staged_pyr ? pitch : 0), o_bear = lay.take(nf * 24),
+                 o_pw = lay.take(nf * 24), o_tr = lay.take(256), o_px = lay.take(nf * 8), o_ini = lay.take(nf);
+    const size_t in_bytes = lay.off;
+    const size_t o_tc = lay.take(256),        // in (seed) and out
+                 o_nt = lay.take(256), o_st = lay.take(sizeof(dsdtm_align_stats));
+    const size_t total = lay.off;
     if (int rc = ensure_stage(ctx, total)) return rc;
     uint8_t* h = (uint8_t*)ctx->h_pinned;
     uint8_t* d = (uint8_t*)ctx->d_stage;
@@ -1139,9 +1167,7 @@ static int sparse_align_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
     // pair, ~17 KB over PCIe) and writes its few results there: no H2D / D2H copy operations around the launch.
     const bool zero_copy = !staged_pyr;
     if (zero_copy) {
-        void* hd = nullptr;
-        HIP_TRY(ctx, hipHostGetDevicePointer(&hd, ctx->h_pinned, 0));
-        d = (uint8_t*)hd;
+        if (int rc = pinned_device_ptr(ctx, &d)) return rc;
         memset(h + o_nt, 0, total - o_nt);
     } else {
         HIP_TRY(ctx, hipMemcpyAsync(d, h, in_bytes + 256, hipMemcpyHostToDevice, ctx->stream));
@@ -1202,9 +1228,7 @@ extern "C" int dsdtm_sparse_align(dsdtm_ctx* ctx, const dsdtm_pyramid* ref, cons
     PackedPyr pr, pc;
     if (int rc = plan_pyramid(ctx, ref, &pr)) return rc;
     if (int rc = plan_pyramid(ctx, cur, &pc)) return rc;
-    if (pr.levels != pc.levels) { set_err(ctx, "ref/cur pyramids differ in level count"); return DSDTM_ERR_INVALID; }
-    for (int l = 0; l < pr.levels; ++l)
-        if (pr.w[l] != pc.w[l] || pr.h[l] != pc.h[l]) { set_err(ctx, "ref/cur level %d differ in size", l); return DSDTM_ERR_INVALID; }
+    if (int rc = check_ref_cur_geometry(ctx, pr, pc)) return rc;
     return sparse_align_one(ctx, pr, ref, cur, nullptr, nullptr, 0, cam, px_xy, bearing, p_world, initial, n_features,
                             T_ref_w, T_cur_w, prm, n_tracked, stats);
 }
@@ -1560,15 +1584,12 @@ extern "C" int dsdtm_frame_lift(dsdtm_ctx* ctx, const dsdtm_frame* f, const dsdt
     if (!lift_launch) { set_err(ctx, "lift: this build has no depth kernels"); return DSDTM_ERR_INVALID; }
     if (n == 0) return DSDTM_OK;
     const size_t N = (size_t)n;
-    size_t o = 0;
-    const size_t o_px = o; o += align_up(N * 8, 256);
-    const size_t o_d = o; o += align_up(N * 4, 256);
-    const size_t o_p = o; o += align_up(N * 24, 256);
-    if (int rc = ensure_stage(ctx, o)) return rc;
+    StageLayout lay;
+    const size_t o_px = lay.take(N * 8), o_d = lay.take(N * 4), o_p = lay.take(N * 24);
+    if (int rc = ensure_stage(ctx, lay.off)) return rc;
     uint8_t* h = (uint8_t*)ctx->h_pinned;
-    void* hd_ = nullptr;
-    HIP_TRY(ctx, hipHostGetDevicePointer(&hd_, ctx->h_pinned, 0));
-    uint8_t* hd = (uint8_t*)hd_;
+    uint8_t* hd = nullptr;
+    if (int rc = pinned_device_ptr(ctx, &hd)) return rc;
     memcpy(h + o_px, px_xy, N * 8);
     // every input is read once and every result written once: straight from / to the pinned block
     LiftArgs a;
@@ -1597,35 +1618,41 @@ extern "C" int dsdtm_sparse_align_frames(dsdtm_ctx* ctx, const dsdtm_frame* ref,
         set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID;
     }
     if (ref->owner != ctx || cur->owner != ctx) { set_err(ctx, "frame belongs to another context"); return DSDTM_ERR_INVALID; }
-    if (ref->pl.levels != cur->pl.levels) { set_err(ctx, "ref/cur pyramids differ in level count"); return DSDTM_ERR_INVALID; }
-    for (int l = 0; l < ref->pl.levels; ++l)
-        if (ref->pl.w[l] != cur->pl.w[l] || ref->pl.h[l] != cur->pl.h[l]) { set_err(ctx, "ref/cur level %d differ in size", l); return DSDTM_ERR_INVALID; }
+    if (int rc = check_ref_cur_geometry(ctx, ref->pl, cur->pl)) return rc;
     return sparse_align_one(ctx, ref->pl, nullptr, nullptr, ref->d, cur->d, ref->pitch, cam, px_xy, bearing, p_world, initial,
                             n_features, T_ref_w, T_cur_w, prm, n_tracked, stats, ref->seq > cur->seq ? ref->seq : cur->seq);
 }
 
 // ---- feature detector (per-cell part) ----------------------------------------------------------
-static int detect_cells_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyramid* host_pyr, const uint8_t* dev_pyr,
-                            const uint8_t* grid_occupied, const dsdtm_detect_params* prm, float* cell_score,
-                            int32_t* cell_x, int32_t* cell_y, int32_t* cell_level, unsigned long long frame_seq = 0) {
-    if (!prm || !cell_score || !cell_x || !cell_y || !cell_level) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
-    if (prm->cell_size <= 0 || prm->grid_cols <= 0 || prm->grid_rows <= 0 || prm->levels <= 0 || prm->levels > pl.levels ||
+// levels: of the pyramid the detector is to run on
+static int check_detect_params(dsdtm_ctx* ctx, const dsdtm_detect_params* prm, int levels) {
+    if (prm->cell_size <= 0 || prm->grid_cols <= 0 || prm->grid_rows <= 0 || prm->levels <= 0 || prm->levels > levels ||
         prm->barrier < 0 || prm->barrier > 254 || !(prm->detection_threshold >= 0.0f) ||
         (long long)prm->grid_cols * prm->grid_rows > (1 << 24)) {
         set_err(ctx, "bad detector parameters"); return DSDTM_ERR_INVALID;
     }
+    return DSDTM_OK;
+}
+// what both detector entries pass on from the parameters
+static void fill_detect_params(DetectArgs& a, const dsdtm_detect_params* prm, size_t pyr_pitch, int n_frames) {
+    a.pyr_pitch = pyr_pitch; a.n_frames = n_frames; a.levels = prm->levels;
+    a.cell_size = prm->cell_size; a.grid_cols = prm->grid_cols; a.grid_rows = prm->grid_rows; a.barrier = prm->barrier;
+    a.detection_threshold = prm->detection_threshold;
+}
+static int detect_cells_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyramid* host_pyr, const uint8_t* dev_pyr,
+                            const uint8_t* grid_occupied, const dsdtm_detect_params* prm, float* cell_score,
+                            int32_t* cell_x, int32_t* cell_y, int32_t* cell_level, unsigned long long frame_seq = 0) {
+    if (!prm || !cell_score || !cell_x || !cell_y || !cell_level) { set_err(ctx, "NULL argument"); return DSDTM_ERR_INVALID; }
+    if (int rc = check_detect_params(ctx, prm, pl.levels)) return rc;
     for (int l = 0; l < prm->levels; ++l)
         if (pl.w[l] >= (1 << 14) || pl.h[l] >= (1 << 14)) { set_err(ctx, "level %d larger than 16383 pixels", l); return DSDTM_ERR_INVALID; }
     const size_t G = (size_t)prm->grid_cols * prm->grid_rows;
     const size_t pitch = align_up(pl.bytes, 256);
-    size_t o = 0;
-    const size_t o_pyr = o; if (!dev_pyr) o += pitch;
-    const size_t o_occ = o; o += align_up(G, 256);
-    const size_t in_bytes = o;
-    const size_t o_key = o; o += align_up(G * 8, 256);
-    const size_t o_score = o; o += pitch;
-    const size_t total = o;
-    if (int rc = ensure_stage(ctx, total)) return rc;
+    StageLayout lay;
+    const size_t o_pyr = lay.take(dev_pyr ? 0 : pitch), o_occ = lay.take(G);
+    const size_t in_bytes = lay.off;
+    const size_t o_key = lay.take(G * 8), o_score = lay.take(pitch);
+    if (int rc = ensure_stage(ctx, lay.off)) return rc;
     uint8_t* h = (uint8_t*)ctx->h_pinned;
     uint8_t* d = (uint8_t*)ctx->d_stage;
     if (!dev_pyr) pack_pyramid(host_pyr, pl, h + o_pyr);
@@ -1637,10 +1664,8 @@ static int detect_cells_one(dsdtm_ctx* ctx, const PackedPyr& pl, const dsdtm_pyr
     memset(&a, 0, sizeof a);
     a.pyr = dev_pyr ? dev_pyr : d + o_pyr; a.score = d + o_score; a.cell_key = (unsigned long long*)(d + o_key);
     a.occupied = d + o_occ;
-    a.pyr_pitch = pitch; a.n_frames = 1; a.levels = prm->levels;
-    a.cell_size = prm->cell_size; a.grid_cols = prm->grid_cols; a.grid_rows = prm->grid_rows; a.barrier = prm->barrier;
-    a.detection_threshold = prm->detection_threshold;
-    for (int l = 0; l < prm->levels; ++l) { a.lv[l].w = pl.w[l]; a.lv[l].h = pl.h[l]; a.lv[l].stride = pl.w[l]; a.lv[l].off = (uint32_t)pl.off[l]; }
+    fill_detect_params(a, prm, pitch, 1);
+    fill_levels(a.lv, pl, prm->levels);
     HIP_TRY(ctx, detect_launch(a, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(h + o_key, d + o_key, G * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1685,9 +1710,7 @@ extern "C" int dsdtm_detect_cells_batch_device(dsdtm_ctx* ctx, const uint8_t* py
     if (!ctx) return DSDTM_ERR_INVALID;
     if (!pyr || !width || !height || !stride || !level_offset || !prm || !score_scratch || !key_scratch || !cell_score || !cell_x ||
         !cell_y || !cell_level || n_frames < 0 || levels <= 0 || levels > DSDTM_MAX_LEVELS) { set_err(ctx, "bad argument"); return DSDTM_ERR_INVALID; }
-    if (prm->cell_size <= 0 || prm->grid_cols <= 0 || prm->grid_rows <= 0 || prm->levels <= 0 || prm->levels > levels ||
-        prm->barrier < 0 || prm->barrier > 254 || !(prm->detection_threshold >= 0.0f) ||
-        (long long)prm->grid_cols * prm->grid_rows > (1 << 24)) { set_err(ctx, "bad detector parameters"); return DSDTM_ERR_INVALID; }
+    if (int rc = check_detect_params(ctx, prm, levels)) return rc;
     // the kernels fetch pyramid and score rows as dwords and index frames through the grid's z dimension
     if ((pyr_pitch & 3) || (((size_t)pyr) & 3) || (((size_t)score_scratch) & 3)) {
         set_err(ctx, "detector batch: pyramid base, score scratch and pyr_pitch must be 4-byte aligned"); return DSDTM_ERR_INVALID;
@@ -1700,17 +1723,14 @@ extern "C" int dsdtm_detect_cells_batch_device(dsdtm_ctx* ctx, const uint8_t* py
     if (n_frames == 0) return DSDTM_OK;
     DetectArgs a;
     memset(&a, 0, sizeof a);
-    for (int l = 0; l < prm->levels; ++l) {
-        if (width[l] <= 0 || height[l] <= 0 || stride[l] < width[l] || width[l] >= (1 << 14) || height[l] >= (1 << 14) ||
-            level_offset[l] + (size_t)stride[l] * height[l] > pyr_pitch) { set_err(ctx, "level %d does not fit", l); return DSDTM_ERR_INVALID; }
-        a.lv[l].w = width[l]; a.lv[l].h = height[l]; a.lv[l].stride = stride[l]; a.lv[l].off = (uint32_t)level_offset[l];
-    }
+    for (int l = 0; l < prm->levels; ++l)       // (level by level with the size limit of the cell keys: the first bad level is the one named)
+        if (width[l] >= (1 << 14) || height[l] >= (1 << 14) || !level_fits(l, width, height, stride, level_offset, pyr_pitch, a.lv)) {
+            set_err(ctx, "level %d does not fit", l); return DSDTM_ERR_INVALID;
+        }
     const size_t G = (size_t)prm->grid_cols * prm->grid_rows;
     a.pyr = pyr; a.score = score_scratch; a.cell_key = key_scratch; a.occupied = grid_occupied;
     a.cell_score = cell_score; a.cell_x = cell_x; a.cell_y = cell_y; a.cell_level = cell_level;
-    a.pyr_pitch = pyr_pitch; a.n_frames = n_frames; a.levels = prm->levels;
-    a.cell_size = prm->cell_size; a.grid_cols = prm->grid_cols; a.grid_rows = prm->grid_rows; a.barrier = prm->barrier;
-    a.detection_threshold = prm->detection_threshold;
+    fill_detect_params(a, prm, pyr_pitch, n_frames);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemsetAsync(key_scratch, 0, (size_t)n_frames * G * 8, (hipStream_t)hip_stream));
     HIP_TRY(ctx, detect_launch(a, (hipStream_t)hip_stream));
@@ -1757,14 +1777,7 @@ extern "C" int dsdtm_align2d_batch_device(dsdtm_ctx* ctx, const dsdtm_image_desc
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     A2DKernelArgs a;
     memset(&a, 0, sizeof a);
-    for (int l = 0; l < cur->levels; ++l) {
-        const size_t end = cur->level_offset[l] + (size_t)cur->stride[l] * cur->height[l];
-        if (cur->width[l] <= 0 || cur->height[l] <= 0 || cur->stride[l] < cur->width[l] || end > cur->bytes) {
-            set_err(ctx, "level %d does not fit inside the packed pyramid", l); return DSDTM_ERR_INVALID;
-        }
-        a.lv[l].w = cur->width[l]; a.lv[l].h = cur->height[l]; a.lv[l].stride = cur->stride[l];
-        a.lv[l].off = (uint32_t)cur->level_offset[l];
-    }
+    if (int rc = check_levels(ctx, cur->levels, cur->width, cur->height, cur->stride, cur->level_offset, cur->bytes, "", "the packed pyramid", a.lv)) return rc;
     a.cur_pyr = cur->data; a.patch_border = patch_border; a.patch = patch; a.level = level;
     a.px_xy = px_xy; a.converged = converged; a.m = m; a.max_iters = max_iters; a.levels = cur->levels;
     HIP_TRY(ctx, align2d_launch(a, (hipStream_t)hip_stream));
@@ -1782,15 +1795,11 @@ extern "C" int dsdtm_align2d_batch(dsdtm_ctx* ctx, const dsdtm_pyramid* cur, con
     for (int i = 0; i < m; ++i)
         if (level[i] < 0 || level[i] >= pc.levels) { set_err(ctx, "level[%d]=%d outside the pyramid", i, level[i]); return DSDTM_ERR_INVALID; }
     const size_t M = (size_t)m;
-    size_t o = 0;
-    const size_t o_pyr = o; o += align_up(pc.bytes, 256);
-    const size_t o_pb = o; o += align_up(M * 100, 256);
-    const size_t o_p = o; o += align_up(M * 64, 256);
-    const size_t o_lv = o; o += align_up(M * 4, 256);
-    const size_t o_px = o; o += align_up(M * 16, 256);
-    const size_t in_bytes = o;
-    const size_t o_cv = o; o += align_up(M, 256);
-    const size_t total = o;
+    StageLayout lay;
+    const size_t o_pyr = lay.take(pc.bytes), o_pb = lay.take(M * 100), o_p = lay.take(M * 64), o_lv = lay.take(M * 4), o_px = lay.take(M * 16);
+    const size_t in_bytes = lay.off;
+    const size_t o_cv = lay.take(M);
+    const size_t total = lay.off;
     if (int rc = ensure_stage(ctx, total)) return rc;
     uint8_t* h = (uint8_t*)ctx->h_pinned;
     uint8_t* d = (uint8_t*)ctx->d_stage;
@@ -1802,8 +1811,7 @@ extern "C" int dsdtm_align2d_batch(dsdtm_ctx* ctx, const dsdtm_pyramid* cur, con
     HIP_TRY(ctx, hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     dsdtm_image_desc img;
     memset(&img, 0, sizeof img);
-    img.levels = pc.levels;
-    for (int l = 0; l < pc.levels; ++l) { img.width[l] = pc.w[l]; img.height[l] = pc.h[l]; img.stride[l] = pc.w[l]; img.level_offset[l] = pc.off[l]; }
+    fill_levels(img, pc);
     img.bytes = pc.bytes; img.data = d + o_pyr;
     if (int rc = dsdtm_align2d_batch_device(ctx, &img, d + o_pb, d + o_p, (const int32_t*)(d + o_lv),
                                             (double*)(d + o_px), d + o_cv, max_iters, m, ctx->stream)) return rc;
@@ -1823,8 +1831,7 @@ extern "C" int dsdtm_pyrdown_batch_device(dsdtm_ctx* ctx, uint8_t* pyr, size_t p
         set_err(ctx, "bad argument"); return DSDTM_ERR_INVALID;
     }
     for (int l = 0; l < levels; ++l) {
-        if (width[l] <= 0 || height[l] <= 0 || stride[l] < width[l] ||
-            level_offset[l] + (size_t)stride[l] * height[l] > pyr_pitch) { set_err(ctx, "level %d does not fit", l); return DSDTM_ERR_INVALID; }
+        if (!level_fits(l, width, height, stride, level_offset, pyr_pitch, nullptr)) { set_err(ctx, "level %d does not fit", l); return DSDTM_ERR_INVALID; }
         if (l > 0 && (width[l] != (width[l - 1] + 1) / 2 || height[l] != (height[l - 1] + 1) / 2)) {
             set_err(ctx, "level %d is not ((w+1)/2,(h+1)/2) of level %d", l, l - 1); return DSDTM_ERR_INVALID;
         }
@@ -1874,6 +1881,46 @@ extern "C" int dsdtm_pyrdown(dsdtm_ctx* ctx, const uint8_t* level0, int width, i
 }
 
 // ---- warp prelude ---------------------------------------------------------------------------
+// The columns of FindMatchDirect's two kernels over m candidates, wherever an entry keeps them
+struct MatchColumns {
+    const double* T_kf_w; const int32_t* cand_kf; const float* ref_px; const int32_t* ref_level; const double* ref_bearing; const double* p_world;
+    double* affine; int32_t* search_level; uint8_t* patch_border; uint8_t* patch;      // written by the warp half ...
+    double* px_xy; uint8_t* converged;                                                  // ... and by Align2D (level-0 pixels)
+};
+// The arguments of the warp prelude on one level table: camera, columns, sizes. The caller adds where the pyramids lie (and, for
+// a batch of current frames, their poses and the candidates' frames).
+static void fill_warp_args(WarpKernelArgs& a, const MatchColumns& c, const dsdtm_camera* cam, const LevelGeom* lv, int levels, int m, int n_kf,
+                           int max_search_level) {
+    memset(&a, 0, sizeof a);
+    a.T_kf_w = c.T_kf_w; a.cand_kf = c.cand_kf; a.ref_px = c.ref_px; a.ref_level = c.ref_level; a.ref_bearing = c.ref_bearing;
+    a.p_world = c.p_world; a.affine = c.affine; a.search_level = c.search_level; a.patch_border = c.patch_border; a.patch = c.patch;
+    a.m = m; a.n_kf = n_kf; a.max_search_level = max_search_level; a.levels = levels;
+    a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
+    for (int l = 0; l < levels; ++l) a.lv[l] = lv[l];
+}
+// ... and of the Align2D that follows it (b), on the prelude's patches and search levels
+static void fill_match_args(WarpKernelArgs& a, A2DKernelArgs& b, const MatchColumns& c, const dsdtm_camera* cam, const LevelGeom* lv, int levels,
+                            int m, int n_kf, int max_search_level, int max_iters) {
+    fill_warp_args(a, c, cam, lv, levels, m, n_kf, max_search_level);
+    memset(&b, 0, sizeof b);
+    b.patch_border = c.patch_border; b.patch = c.patch; b.level = c.search_level; b.px_xy = c.px_xy; b.converged = c.converged;
+    b.m = m; b.max_iters = max_iters; b.levels = levels; b.px_level0 = 1;
+    for (int l = 0; l < levels; ++l) b.lv[l] = lv[l];
+}
+// FindMatchDirect as one kernel, the warped patches in LDS (a.patch_border / a.patch are not touched); the diagnostic build can
+// split it into its two halves (option fmd_split, rounds 1-4), the patches then go through device memory
+static int launch_match(dsdtm_ctx* ctx, WarpKernelArgs& a, const A2DKernelArgs& b, hipStream_t stream) {
+#ifdef DSDTM_DIAG
+    if (options().fmd_split) {
+        HIP_TRY(ctx, warp_launch(a, stream));
+        HIP_TRY(ctx, align2d_launch(b, stream));
+        return DSDTM_OK;
+    }
+#endif
+    a.affine = nullptr; a.no_xcd = options().fmd_no_xcd;                        // (nobody reads the affine maps here)
+    HIP_TRY(ctx, match_launch(a, b, stream));
+    return DSDTM_OK;
+}
 extern "C" int dsdtm_warp_patches(dsdtm_ctx* ctx, const dsdtm_pyramid* kf_pyr, int n_kf, const dsdtm_camera* cam,
                                   const double* T_kf_w, const double T_cur_w[12], const int32_t* cand_kf,
                                   const float* ref_px, const int32_t* ref_level, const double* ref_bearing,
@@ -1890,9 +1937,7 @@ extern "C" int dsdtm_warp_patches(dsdtm_ctx* ctx, const dsdtm_pyramid* kf_pyr, i
     for (int k = 1; k < n_kf; ++k) {
         PackedPyr pk;
         if (int rc = plan_pyramid(ctx, &kf_pyr[k], &pk)) return rc;
-        if (pk.levels != p0.levels || memcmp(pk.w, p0.w, sizeof(int) * p0.levels) || memcmp(pk.h, p0.h, sizeof(int) * p0.levels)) {
-            set_err(ctx, "keyframe %d pyramid geometry differs from keyframe 0", k); return DSDTM_ERR_INVALID;
-        }
+        if (!same_geometry(pk, p0)) { set_err(ctx, "keyframe %d pyramid geometry differs from keyframe 0", k); return DSDTM_ERR_INVALID; }
     }
     for (int i = 0; i < m; ++i) {
         if (cand_kf[i] < 0 || cand_kf[i] >= n_kf || ref_level[i] < 0 || ref_level[i] >= p0.levels) {
@@ -1901,20 +1946,12 @@ extern "C" int dsdtm_warp_patches(dsdtm_ctx* ctx, const dsdtm_pyramid* kf_pyr, i
     }
     const size_t M = (size_t)m;
     const size_t pitch = align_up(p0.bytes, 256);
-    size_t o = 0;
-    const size_t o_pyr = o; o += pitch * (size_t)n_kf;
-    const size_t o_tk = o; o += align_up((size_t)n_kf * 96, 256);
-    const size_t o_rb = o; o += align_up(M * 24, 256);
-    const size_t o_pw = o; o += align_up(M * 24, 256);
-    const size_t o_ck = o; o += align_up(M * 4, 256);
-    const size_t o_rl = o; o += align_up(M * 4, 256);
-    const size_t o_rp = o; o += align_up(M * 8, 256);
-    const size_t in_bytes = o;
-    const size_t o_af = o; o += align_up(M * 32, 256);
-    const size_t o_sl = o; o += align_up(M * 4, 256);
-    const size_t o_pb = o; o += align_up(M * 100, 256);
-    const size_t o_pp = o; o += align_up(M * 64, 256);
-    const size_t total = o;
+    StageLayout lay;
+    const size_t o_pyr = lay.take(pitch * (size_t)n_kf), o_tk = lay.take((size_t)n_kf * 96), o_rb = lay.take(M * 24), o_pw = lay.take(M * 24),
+                 o_ck = lay.take(M * 4), o_rl = lay.take(M * 4), o_rp = lay.take(M * 8);
+    const size_t in_bytes = lay.off;
+    const size_t o_af = lay.take(M * 32), o_sl = lay.take(M * 4), o_pb = lay.take(M * 100), o_pp = lay.take(M * 64);
+    const size_t total = lay.off;
     if (int rc = ensure_stage(ctx, total)) return rc;
     uint8_t* h = (uint8_t*)ctx->h_pinned;
     uint8_t* d = (uint8_t*)ctx->d_stage;
@@ -1926,17 +1963,15 @@ extern "C" int dsdtm_warp_patches(dsdtm_ctx* ctx, const dsdtm_pyramid* kf_pyr, i
     memcpy(h + o_rl, ref_level, M * 4);
     memcpy(h + o_rp, ref_px, M * 8);
     HIP_TRY(ctx, hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const MatchColumns c = {(const double*)(d + o_tk), (const int32_t*)(d + o_ck), (const float*)(d + o_rp), (const int32_t*)(d + o_rl),
+                            (const double*)(d + o_rb), (const double*)(d + o_pw), (double*)(d + o_af), (int32_t*)(d + o_sl), d + o_pb, d + o_pp,
+                            nullptr, nullptr};
+    LevelGeom lv[DSDTM_MAX_LEVELS];
+    fill_levels(lv, p0, p0.levels);
     WarpKernelArgs a;
-    memset(&a, 0, sizeof a);
-    a.kf_pyr = d + o_pyr; a.kf_pitch = pitch; a.T_kf_w = (const double*)(d + o_tk);
-    a.cand_kf = (const int32_t*)(d + o_ck); a.ref_px = (const float*)(d + o_rp);
-    a.ref_level = (const int32_t*)(d + o_rl); a.ref_bearing = (const double*)(d + o_rb);
-    a.p_world = (const double*)(d + o_pw); a.affine = (double*)(d + o_af);
-    a.search_level = (int32_t*)(d + o_sl); a.patch_border = d + o_pb; a.patch = d + o_pp;
+    fill_warp_args(a, c, cam, lv, p0.levels, m, n_kf, max_search_level);
+    a.kf_pyr = d + o_pyr; a.kf_pitch = pitch;
     memcpy(a.T_cur_w, T_cur_w, 96);
-    a.m = m; a.n_kf = n_kf; a.max_search_level = max_search_level; a.levels = p0.levels;
-    a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
-    for (int l = 0; l < p0.levels; ++l) { a.lv[l].w = p0.w[l]; a.lv[l].h = p0.h[l]; a.lv[l].stride = p0.w[l]; a.lv[l].off = (uint32_t)p0.off[l]; }
     HIP_TRY(ctx, warp_launch(a, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(h + o_af, d + o_af, total - o_af, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1966,9 +2001,7 @@ extern "C" int dsdtm_match_candidates_frames(dsdtm_ctx* ctx, const dsdtm_frame* 
         if (!kf[k] || kf[k]->owner != ctx) { set_err(ctx, "keyframe %d: NULL or foreign frame", k); return DSDTM_ERR_INVALID; }
         if (kf[k]->seq > frames_seq) frames_seq = kf[k]->seq;
         const PackedPyr& pk = kf[k]->pl;
-        if (pk.levels != p0.levels || memcmp(pk.w, p0.w, sizeof(int) * p0.levels) || memcmp(pk.h, p0.h, sizeof(int) * p0.levels)) {
-            set_err(ctx, "keyframe %d pyramid geometry differs from the current frame", k); return DSDTM_ERR_INVALID;
-        }
+        if (!same_geometry(pk, p0)) { set_err(ctx, "keyframe %d pyramid geometry differs from the current frame", k); return DSDTM_ERR_INVALID; }
     }
     if (max_search_level < 0 || max_search_level >= p0.levels) { set_err(ctx, "max_search_level outside the pyramid"); return DSDTM_ERR_INVALID; }
     for (int i = 0; i < m; ++i) {
@@ -1977,22 +2010,13 @@ extern "C" int dsdtm_match_candidates_frames(dsdtm_ctx* ctx, const dsdtm_frame* 
         }
     }
     const size_t M = (size_t)m;
-    size_t o = 0;
-    const size_t o_ptr = o; o += align_up((size_t)n_kf * sizeof(void*), 256);
-    const size_t o_tk = o; o += align_up((size_t)n_kf * 96, 256);
-    const size_t o_rb = o; o += align_up(M * 24, 256);
-    const size_t o_pw = o; o += align_up(M * 24, 256);
-    const size_t o_ck = o; o += align_up(M * 4, 256);
-    const size_t o_rl = o; o += align_up(M * 4, 256);
-    const size_t o_rp = o; o += align_up(M * 8, 256);
-    const size_t o_px = o; o += align_up(M * 16, 256);          // in and out
-    const size_t o_sl = o; o += align_up(M * 4, 256);
-    const size_t o_cv = o; o += align_up(M, 256);
-    const size_t o_af = o; o += align_up(M * 32, 256);          // device only
-    const size_t o_pb = o; o += align_up(M * 100, 256);
-    const size_t o_pp = o; o += align_up(M * 64, 256);
-    const size_t total = o;
-    if (int rc = ensure_stage(ctx, total)) return rc;
+    StageLayout lay;
+    const size_t o_ptr = lay.take((size_t)n_kf * sizeof(void*)), o_tk = lay.take((size_t)n_kf * 96), o_rb = lay.take(M * 24), o_pw = lay.take(M * 24),
+                 o_ck = lay.take(M * 4), o_rl = lay.take(M * 4), o_rp = lay.take(M * 8),
+                 o_px = lay.take(M * 16),                                       // in and out
+                 o_sl = lay.take(M * 4), o_cv = lay.take(M),
+                 o_af = lay.take(M * 32), o_pb = lay.take(M * 100), o_pp = lay.take(M * 64);   // device only
+    if (int rc = ensure_stage(ctx, lay.off)) return rc;
     uint8_t* h = (uint8_t*)ctx->h_pinned;
     uint8_t* d = (uint8_t*)ctx->d_stage;
     for (int k = 0; k < n_kf; ++k) ((const uint8_t**)(h + o_ptr))[k] = kf[k]->d;
@@ -2007,36 +2031,20 @@ extern "C" int dsdtm_match_candidates_frames(dsdtm_ctx* ctx, const dsdtm_frame* 
     // Every input is read once per candidate and every result written once: the two kernels take them straight
     // from / to the pinned block (no copy operations around the launches); only the warped patches, which the
     // second kernel re-reads at every iteration, live in device memory.
-    void* hd = nullptr;
-    HIP_TRY(ctx, hipHostGetDevicePointer(&hd, ctx->h_pinned, 0));
-    uint8_t* const io = (uint8_t*)hd;
+    uint8_t* io = nullptr;
+    if (int rc = pinned_device_ptr(ctx, &io)) return rc;
+    const MatchColumns c = {(const double*)(io + o_tk), (const int32_t*)(io + o_ck), (const float*)(io + o_rp), (const int32_t*)(io + o_rl),
+                            (const double*)(io + o_rb), (const double*)(io + o_pw), (double*)(d + o_af), (int32_t*)(io + o_sl), d + o_pb, d + o_pp,
+                            (double*)(io + o_px), io + o_cv};
+    LevelGeom lv[DSDTM_MAX_LEVELS];
+    fill_levels(lv, p0, p0.levels);
     WarpKernelArgs a;
-    memset(&a, 0, sizeof a);
-    a.kf_ptrs = (const uint8_t* const*)(io + o_ptr); a.T_kf_w = (const double*)(io + o_tk);
-    a.cand_kf = (const int32_t*)(io + o_ck); a.ref_px = (const float*)(io + o_rp);
-    a.ref_level = (const int32_t*)(io + o_rl); a.ref_bearing = (const double*)(io + o_rb);
-    a.p_world = (const double*)(io + o_pw); a.affine = (double*)(d + o_af);
-    a.search_level = (int32_t*)(io + o_sl); a.patch_border = d + o_pb; a.patch = d + o_pp;
-    memcpy(a.T_cur_w, T_cur_w, 96);
-    a.m = m; a.n_kf = n_kf; a.max_search_level = max_search_level; a.levels = p0.levels;
-    a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
-    for (int l = 0; l < p0.levels; ++l) { a.lv[l].w = p0.w[l]; a.lv[l].h = p0.h[l]; a.lv[l].stride = p0.w[l]; a.lv[l].off = (uint32_t)p0.off[l]; }
     A2DKernelArgs b;
-    memset(&b, 0, sizeof b);
-    b.cur_pyr = cur->d; b.patch_border = d + o_pb; b.patch = d + o_pp; b.level = (const int32_t*)(io + o_sl);
-    b.px_xy = (double*)(io + o_px); b.converged = io + o_cv; b.m = m; b.max_iters = max_iters; b.levels = p0.levels;
-    b.px_level0 = 1;
-    for (int l = 0; l < p0.levels; ++l) b.lv[l] = a.lv[l];
-#ifdef DSDTM_DIAG
-    if (options().fmd_split) {                 // rounds 1-4 (diagnostic build): two kernels, the warped patches through device memory
-        HIP_TRY(ctx, warp_launch(a, ctx->stream));
-        HIP_TRY(ctx, align2d_launch(b, ctx->stream));
-    } else
-#endif
-    {
-        a.affine = nullptr; a.no_xcd = options().fmd_no_xcd;                    // (nobody reads it here)
-        HIP_TRY(ctx, match_launch(a, b, ctx->stream));
-    }
+    fill_match_args(a, b, c, cam, lv, p0.levels, m, n_kf, max_search_level, max_iters);
+    a.kf_ptrs = (const uint8_t* const*)(io + o_ptr);
+    memcpy(a.T_cur_w, T_cur_w, 96);
+    b.cur_pyr = cur->d;
+    if (int rc = launch_match(ctx, a, b, ctx->stream)) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     frames_settle(ctx);
     memcpy(px_xy, h + o_px, M * 16);
@@ -2065,43 +2073,25 @@ extern "C" int dsdtm_match_candidates_batch_device(dsdtm_ctx* ctx, const uint8_t
     if (((size_t)scratch) & 15) { set_err(ctx, "scratch must be 16-byte aligned (the warped patches are written as whole dwords)"); return DSDTM_ERR_INVALID; }
     if (m == 0) return DSDTM_OK;
     const size_t M = (size_t)m;
+    LevelGeom lv[DSDTM_MAX_LEVELS];
+    if (int rc = check_levels(ctx, levels, width, height, stride, level_offset, pyr_pitch, "", "pyr_pitch", lv)) return rc;
+    StageLayout lay;                                            // of `scratch`: M x 32, then M x 100, then M x 64 (256-byte aligned sections)
+    const size_t o_af = lay.take(M * 32), o_pb = lay.take(M * 100), o_pp = lay.take(M * 64);
+    const MatchColumns c = {T_kf_w, cand_kf, ref_px, ref_level, ref_bearing, p_world, (double*)(scratch + o_af), search_level, scratch + o_pb,
+                            scratch + o_pp, px_xy, converged};
     WarpKernelArgs a;
-    memset(&a, 0, sizeof a);
-    for (int l = 0; l < levels; ++l) {
-        if (width[l] <= 0 || height[l] <= 0 || stride[l] < width[l] || level_offset[l] + (size_t)stride[l] * height[l] > pyr_pitch) {
-            set_err(ctx, "level %d does not fit", l); return DSDTM_ERR_INVALID;
-        }
-        a.lv[l].w = width[l]; a.lv[l].h = height[l]; a.lv[l].stride = stride[l]; a.lv[l].off = (uint32_t)level_offset[l];
-    }
-    uint8_t* affine = scratch;                                  // M x 32, then M x 100, then M x 64 (256-byte aligned sections)
-    uint8_t* pb = scratch + align_up(M * 32, 256);
-    uint8_t* pp = pb + align_up(M * 100, 256);
-    a.kf_pyr = kf_pyr; a.kf_pitch = pyr_pitch; a.T_kf_w = T_kf_w; a.T_cur_w_arr = T_cur_w; a.cand_frame = cand_frame;
-    a.cand_kf = cand_kf; a.ref_px = ref_px; a.ref_level = ref_level; a.ref_bearing = ref_bearing; a.p_world = p_world;
-    a.affine = (double*)affine; a.search_level = search_level; a.patch_border = pb; a.patch = pp;
-    a.m = m; a.n_kf = n_kf; a.max_search_level = max_search_level; a.levels = levels; a.n_frames = n_frames;
-    a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     A2DKernelArgs b;
-    memset(&b, 0, sizeof b);
-    b.cur_pyr = cur_pyr; b.patch_border = pb; b.patch = pp; b.level = search_level; b.px_xy = px_xy; b.converged = converged;
-    b.m = m; b.max_iters = max_iters; b.levels = levels; b.px_level0 = 1; b.frame = cand_frame; b.n_frames = n_frames; b.pyr_pitch = pyr_pitch;
-    for (int l = 0; l < levels; ++l) b.lv[l] = a.lv[l];
-#ifdef DSDTM_DIAG
-    if (options().fmd_split) {                 // rounds 1-4 (diagnostic build): two kernels, the warped patches through `scratch`
-        HIP_TRY(ctx, warp_launch(a, (hipStream_t)hip_stream));
-        HIP_TRY(ctx, align2d_launch(b, (hipStream_t)hip_stream));
-    } else
-#endif
-    {                                          // one kernel, the patches stay in LDS (`scratch` is not touched)
-        a.affine = nullptr; a.no_xcd = options().fmd_no_xcd;
-        HIP_TRY(ctx, match_launch(a, b, (hipStream_t)hip_stream));
-    }
-    return DSDTM_OK;
+    fill_match_args(a, b, c, cam, lv, levels, m, n_kf, max_search_level, max_iters);
+    a.kf_pyr = kf_pyr; a.kf_pitch = pyr_pitch; a.T_cur_w_arr = T_cur_w; a.cand_frame = cand_frame; a.n_frames = n_frames;
+    b.cur_pyr = cur_pyr; b.frame = cand_frame; b.n_frames = n_frames; b.pyr_pitch = pyr_pitch;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return launch_match(ctx, a, b, (hipStream_t)hip_stream);    // (fused: `scratch` is not touched)
 }
 extern "C" size_t dsdtm_match_candidates_scratch_bytes(int m) {
+    StageLayout lay;                                            // (the sections of dsdtm_match_candidates_batch_device)
     const size_t M = m > 0 ? (size_t)m : 0;
-    return align_up(M * 32, 256) + align_up(M * 100, 256) + align_up(M * 64, 256);
+    lay.take(M * 32); lay.take(M * 100); lay.take(M * 64);
+    return lay.off;
 }
 
 // ---- Optimizer::PoseOptimization ---------------------------------------------------------------
@@ -2142,6 +2132,7 @@ extern "C" int dsdtm_pose_optimization(dsdtm_ctx* ctx, const double* bearing, co
             set_err(ctx, "feature %d: level %d out of range", i, level[i]); return DSDTM_ERR_INVALID;
         }
     const size_t N = (size_t)n_features;
+    // (not a StageLayout: the columns are packed and this ladder rounds sizes, not offsets — `use` starts right behind `level`)
     size_t o = 0;
     const size_t o_T = o;   o += 12 * 8;                       // in/out
     const size_t o_sm = o;  o += align_up(sizeof(dsdtm_pose_opt_summary), 8);   // out
@@ -2168,9 +2159,7 @@ extern "C" int dsdtm_pose_optimization(dsdtm_ctx* ctx, const double* bearing, co
     // and are copied to the device first.
     const bool zero_copy = n_features > 64 && n_features <= 512;
     if (zero_copy) {
-        void* hd = nullptr;
-        HIP_TRY(ctx, hipHostGetDevicePointer(&hd, ctx->h_pinned, 0));
-        d = (uint8_t*)hd;
+        if (int rc = pinned_device_ptr(ctx, &d)) return rc;
     } else {
         HIP_TRY(ctx, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, ctx->stream));
     }
@@ -2476,7 +2465,7 @@ static void bind_track_kernels(const TrackLayout& L, uint8_t* g, uint8_t* hd, co
     t.po_bearing = (double*)(g + L.g_pob); t.po_world = (double*)(g + L.g_pow); t.po_level = (int32_t*)(g + L.g_pol); t.po_use = g + L.g_pou;
     t.po_n = (int32_t*)(g + L.g_pon);
     memset(&wa, 0, sizeof wa);
-    for (int l = 0; l < pl.levels; ++l) { wa.lv[l].w = pl.w[l]; wa.lv[l].h = pl.h[l]; wa.lv[l].stride = pl.w[l]; wa.lv[l].off = (uint32_t)pl.off[l]; }
+    fill_levels(wa.lv, pl, pl.levels);
     wa.kf_ptrs = t.kf_ptrs; wa.T_kf_w = t.T_kf_w; wa.T_cur_w_arr = t.T_run; wa.cand_frame = t.cand_frame;
     wa.cand_kf = t.cand_kf; wa.ref_px = t.ref_px; wa.ref_level = t.ref_level; wa.ref_bearing = t.ref_bearing; wa.p_world = t.pw;
     wa.search_level = t.search_level; wa.m = columns; wa.n_kf = n_kf; wa.max_search_level = plan.max_search_level; wa.levels = pl.levels;
@@ -2576,9 +2565,8 @@ static int track_frame_impl(dsdtm_ctx* ctx, const dsdtm_camera* cam, const dsdtm
     if (int rc = ensure_stage(ctx, L.h_total > L.g_total ? L.h_total : L.g_total)) return rc;
     uint8_t* h = (uint8_t*)ctx->h_pinned;
     uint8_t* g = (uint8_t*)ctx->d_stage;
-    void* hd_ = nullptr;
-    HIP_TRY(ctx, hipHostGetDevicePointer(&hd_, ctx->h_pinned, 0));
-    uint8_t* hd = (uint8_t*)hd_;                       // the pinned block as the device sees it
+    uint8_t* hd = nullptr;                             // the pinned block as the device sees it
+    if (int rc = pinned_device_ptr(ctx, &hd)) return rc;
     hipStream_t stream = ctx->stream;
     dsdtm_frame* f = cur;
     if (!cur) { if (int rc = frame_alloc(ctx, pl, stream, &f)) return rc; }
@@ -2911,10 +2899,7 @@ static int tracks_layout(dsdtm_ctx* ctx, TrackBatch& B) {
     if (int rc = ensure_stage(ctx, L.h_total > L.g_total ? L.h_total : L.g_total)) return rc;
     B.h = (uint8_t*)ctx->h_pinned;
     B.g = (uint8_t*)ctx->d_stage;
-    void* hd_ = nullptr;
-    HIP_TRY(ctx, hipHostGetDevicePointer(&hd_, ctx->h_pinned, 0));
-    B.hd = (uint8_t*)hd_;
-    return DSDTM_OK;
+    return pinned_device_ptr(ctx, &B.hd);
 }
 
 // Run's range: features, poses seeded (src/Tracking.cpp:201), counts and statistics cleared

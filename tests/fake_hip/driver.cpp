@@ -1,7 +1,9 @@
 // tests/fake_hip/driver.cpp — scenarios that drive the HOST side of the C ABI (dsdtm_amd/csrc/api.cpp: stream rings, pair
 // counters, recover slots, the team epoch, the sharded / streamed entries, frames, the single-call entries' packing) against the
 // fake HIP runtime, under AddressSanitizer + UBSan (or ThreadSanitizer for the two-thread scenario). TEST INFRASTRUCTURE ONLY.
-//   usage: driver [scenario ...]      (no argument: all of them); prints "ok <name>" per scenario, exits non-zero on failure
+//   usage: driver [--trace] [scenario ...]   (no scenario: all of them); prints "ok <name>" per scenario, exits non-zero on failure
+//   --trace: behind every scenario, the call counts, copies (kind, bytes) and launch log it left (fake_hip_print_trace) — two
+//   builds of api.cpp that print the same trace make the same calls in the same order with the same sizes
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -323,6 +325,190 @@ static bool single_call_entries() {
     return true;
 }
 
+// "device" arrays of a scenario (hipMalloc of the fake, zeroed), released together
+struct DeviceArrays {
+    std::vector<void*> mem;
+    template <class T> T* get(size_t count) {
+        void* p = nullptr;
+        if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) std::abort();
+        std::memset(p, 0, count * sizeof(T));
+        mem.push_back(p);
+        return (T*)p;
+    }
+    ~DeviceArrays() { for (void* p : mem) (void)hipFree(p); }
+};
+// the arguments of the device-side stage entries on the driver's geometry: 2 frames, 1 keyframe, 4 candidates, 4 features per frame
+struct StageArgs {
+    static const int F = 2, M = 4;
+    Geometry g = geometry();
+    dsdtm_detect_params dp{8, (W + 7) / 8, (H + 7) / 8, L, 20, 5.0f};
+    size_t G = (size_t)dp.grid_cols * dp.grid_rows;
+    dsdtm_pose_opt_params pop{100, 0};
+    DeviceArrays d;
+    uint8_t *pyr, *kf, *score, *scratch, *conv, *pb, *pp, *use;
+    unsigned long long* keys;
+    float *cell_score, *ref_px;
+    int32_t *cx, *cy, *cl, *cand_frame, *cand_kf, *ref_level, *search_level, *level;
+    double *T_kf, *T_cur, *bearing, *p_world, *px, *rn;
+    dsdtm_pose_opt_summary* sm;
+    StageArgs() {
+        pyr = d.get<uint8_t>(F * g.pitch); kf = d.get<uint8_t>(g.pitch); score = d.get<uint8_t>(F * g.pitch);
+        keys = d.get<unsigned long long>(F * G); cell_score = d.get<float>(F * G);
+        cx = d.get<int32_t>(F * G); cy = d.get<int32_t>(F * G); cl = d.get<int32_t>(F * G);
+        scratch = d.get<uint8_t>(dsdtm_match_candidates_scratch_bytes(M)); conv = d.get<uint8_t>(M);
+        pb = d.get<uint8_t>(M * 100); pp = d.get<uint8_t>(M * 64); use = d.get<uint8_t>(F * M);
+        ref_px = d.get<float>(M * 2); cand_frame = d.get<int32_t>(M); cand_kf = d.get<int32_t>(M); ref_level = d.get<int32_t>(M);
+        search_level = d.get<int32_t>(M); level = d.get<int32_t>(F * M);
+        T_kf = d.get<double>(12); T_cur = d.get<double>(F * 12); bearing = d.get<double>(F * M * 3); p_world = d.get<double>(F * M * 3);
+        px = d.get<double>(M * 2); rn = d.get<double>(F * M); sm = d.get<dsdtm_pose_opt_summary>(F);
+        for (int i = 0; i < M; ++i) cand_frame[i] = i % F;
+    }
+    dsdtm_image_desc image() const {
+        dsdtm_image_desc im{};
+        im.levels = L; im.bytes = g.pitch; im.data = pyr;
+        for (int l = 0; l < L; ++l) { im.width[l] = g.w[l]; im.height[l] = g.h[l]; im.stride[l] = g.st[l]; im.level_offset[l] = g.off[l]; }
+        return im;
+    }
+    // the four entries that take the level table as arrays, with geometry `q` (the pitch stays g.pitch)
+    int detect(dsdtm_ctx* ctx, const Geometry& q, hipStream_t st) {
+        return dsdtm_detect_cells_batch_device(ctx, pyr, g.pitch, F, L, q.w, q.h, q.st, q.off, nullptr, &dp, score, keys, cell_score, cx, cy, cl, st);
+    }
+    int match(dsdtm_ctx* ctx, const Geometry& q, hipStream_t st) {
+        const dsdtm_camera cam = camera();
+        return dsdtm_match_candidates_batch_device(ctx, pyr, F, kf, 1, g.pitch, L, q.w, q.h, q.st, q.off, &cam, T_kf, T_cur, cand_frame, cand_kf, ref_px,
+                                                   ref_level, bearing, p_world, 1, 10, M, scratch, px, search_level, conv, st);
+    }
+    int pyrdown(dsdtm_ctx* ctx, const Geometry& q, hipStream_t st) { return dsdtm_pyrdown_batch_device(ctx, pyr, g.pitch, F, L, q.w, q.h, q.st, q.off, st); }
+    int align2d(dsdtm_ctx* ctx, const dsdtm_image_desc& im, hipStream_t st) { return dsdtm_align2d_batch_device(ctx, &im, pb, pp, search_level, px, conv, 10, M, st); }
+};
+static long launches_so_far() {
+    long n = 0;
+    for (const char* api : {"sparse_align_launch", "sparse_align_launch_team", "detect_launch", "align2d_launch", "pyrdown_launch", "ingest_launch",
+                            "warp_launch", "match_launch", "pose_opt_launch", "track_match_launch", "track_replay_launch"}) n += fake_hip_calls(api);
+    return n;
+}
+
+// ---- 9b. the entries whose arrays are already on the device (single_call_entries reaches them only through the host entries) ----
+static bool device_batch_entries() {
+    dsdtm_ctx* ctx = nullptr;
+    CHECK(dsdtm_create(0, &ctx) == DSDTM_OK);
+    hipStream_t st;
+    CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess);
+    {
+        StageArgs a;
+        std::vector<uint8_t> img((size_t)W * H, 3);
+        dsdtm_frame* f = nullptr;
+        CHECK(dsdtm_frame_create_from_image(ctx, img.data(), W, H, W, L, &f) == DSDTM_OK);
+        std::vector<float> sc(a.G);
+        std::vector<int32_t> cx(a.G), cy(a.G), cl(a.G);
+        CHECK(dsdtm_detect_cells_frame(ctx, f, nullptr, &a.dp, sc.data(), cx.data(), cy.data(), cl.data()) == DSDTM_OK);
+        CHECK(sc[0] == a.dp.detection_threshold && cl[a.G - 1] == 0);            // (the fake kernel leaves every cell empty)
+        dsdtm_frame_destroy(ctx, f);
+        CHECK(a.detect(ctx, a.g, st) == DSDTM_OK);
+        CHECK(a.match(ctx, a.g, st) == DSDTM_OK);
+        CHECK(a.align2d(ctx, a.image(), st) == DSDTM_OK);
+        CHECK(a.pyrdown(ctx, a.g, st) == DSDTM_OK);
+        CHECK(dsdtm_pose_optimization_batch_device(ctx, StageArgs::F, StageArgs::M, nullptr, a.bearing, a.p_world, a.level, a.use, a.T_cur, &a.pop,
+                                                   a.rn, a.sm, st) == DSDTM_OK);
+        CHECK(fake_hip_pending() > 0);                                           // asynchronous: nothing has run yet
+        CHECK(hipStreamSynchronize(st) == hipSuccess);
+        CHECK(a.cell_score[2 * a.G - 1] == a.dp.detection_threshold && a.conv[StageArgs::M - 1] == 1 && a.sm[1].termination == DSDTM_PO_NO_RESIDUALS);
+        CHECK(a.pyr[a.g.pitch + a.g.off[2]] == 0x11);                            // pyrDown wrote the second image's last level
+    }
+    CHECK(no_fake_errors());
+    dsdtm_destroy(ctx);
+    CHECK(hipStreamDestroy(st) == hipSuccess);
+    CHECK(fake_hip_live_allocations() == 0);
+    return true;
+}
+
+// ---- 9c. a level table that does not fit: refused by every entry that takes one, before anything is launched; then a context
+//          that is named twice in a shard list ----
+static bool refused_levels() {
+    dsdtm_ctx* ctx = nullptr;
+    CHECK(dsdtm_create(0, &ctx) == DSDTM_OK);
+    const dsdtm_camera cam = camera(); const dsdtm_align_params prm = params();
+    {
+        StageArgs a;
+        Geometry past = a.g, narrow = a.g;
+        past.off[L - 1] = a.g.pitch - (size_t)a.g.st[L - 1] * a.g.h[L - 1] + 1;   // the last level ends one byte past the pitch
+        narrow.st[1] = a.g.w[1] - 1;                                             // a row shorter than its pixels
+        Batch dev(2, 100, true), host(2, 100, false);
+        const long launches0 = launches_so_far();
+        for (const Geometry* q : {&past, &narrow}) {
+            auto refused = [&](int rc) { return rc == DSDTM_ERR_INVALID && std::strstr(dsdtm_last_error(ctx), "does not fit") != nullptr; };
+            for (Batch* bt : {&dev, &host}) for (int l = 0; l < L; ++l) { bt->b.stride[l] = q->st[l]; bt->b.level_offset[l] = q->off[l]; }
+            dsdtm_image_desc im = a.image();
+            for (int l = 0; l < L; ++l) { im.stride[l] = q->st[l]; im.level_offset[l] = q->off[l]; }
+            CHECK(refused(dsdtm_sparse_align_batch_device(ctx, &dev.b, &cam, &prm, nullptr)));
+            dsdtm_ctx* one[1] = {ctx};
+            CHECK(refused(dsdtm_sparse_align_batch_sharded(one, 1, &host.b, &cam, &prm)));
+            CHECK(refused(a.detect(ctx, *q, nullptr)));
+            CHECK(refused(a.align2d(ctx, im, nullptr)));
+            CHECK(refused(a.pyrdown(ctx, *q, nullptr)));
+            CHECK(refused(a.match(ctx, *q, nullptr)));
+        }
+        CHECK(launches_so_far() == launches0 && fake_hip_pending() == 0 && fake_hip_calls("hipMemcpyAsync") == 0);
+        // one context per shard
+        for (int l = 0; l < L; ++l) { host.b.stride[l] = a.g.st[l]; host.b.level_offset[l] = a.g.off[l]; }
+        dsdtm_ctx* other = nullptr;
+        CHECK(dsdtm_create(0, &other) == DSDTM_OK);
+        dsdtm_ctx* twice[3] = {ctx, other, ctx};
+        std::vector<uint8_t> ref((size_t)3 * W * H, 9);
+        dsdtm_stream_desc s{};
+        s.n_pairs = 2; s.max_features = 100; s.levels = L; s.width = W; s.height = H; s.row_stride = W; s.image_pitch = (size_t)W * H;
+        s.ref_image = ref.data();
+        s.px_xy = host.b.px_xy; s.bearing = host.b.bearing; s.p_world = host.b.p_world; s.initial = host.b.initial;
+        s.T_ref_w = host.b.T_ref_w; s.T_cur_w = host.b.T_cur_w; s.n_tracked = host.b.n_tracked;
+        CHECK(dsdtm_sparse_align_batch_sharded(twice, 3, &host.b, &cam, &prm) == DSDTM_ERR_INVALID && std::strstr(dsdtm_last_error(ctx), "sharded batch:") &&
+              std::strstr(dsdtm_last_error(ctx), "appears twice"));
+        CHECK(dsdtm_sparse_align_batch_streamed(twice, 3, &s, 2, &cam, &prm) == DSDTM_ERR_INVALID && std::strstr(dsdtm_last_error(ctx), "streamed batch:") &&
+              std::strstr(dsdtm_last_error(ctx), "appears twice"));
+        twice[1] = nullptr;
+        CHECK(dsdtm_sparse_align_batch_sharded(twice, 3, &host.b, &cam, &prm) == DSDTM_ERR_INVALID);
+        CHECK(dsdtm_sparse_align_batch_streamed(twice, 3, &s, 2, &cam, &prm) == DSDTM_ERR_INVALID);
+        CHECK(launches_so_far() == launches0 && fake_hip_pending() == 0);
+        dsdtm_destroy(other);
+    }
+    dsdtm_destroy(ctx);
+    CHECK(fake_hip_live_allocations() == 0);
+    return true;
+}
+
+// ---- 9d. the sharded and the streamed entry on ONE context (one thread: the order and size of every copy is the same in every
+//          run), with and without the optional n_features / stats columns, whose places in the staging block are then empty ----
+static bool host_batch_one_context() {
+    dsdtm_ctx* ctx = nullptr;
+    CHECK(dsdtm_create(0, &ctx) == DSDTM_OK);
+    const dsdtm_camera cam = camera(); const dsdtm_align_params prm = params();
+    dsdtm_ctx* one[1] = {ctx};
+    for (int optional = 0; optional < 2; ++optional) {
+        const int P = 5, N = optional ? 600 : 0;                 // (no features at all; teams of three)
+        Batch hb(P, N, false);
+        std::vector<int32_t> nf(P, N);
+        if (optional) hb.b.n_features = nf.data(); else hb.b.stats = nullptr;
+        CHECK(dsdtm_sparse_align_batch_sharded(one, 1, &hb.b, &cam, &prm) == DSDTM_OK);
+        for (int i = 0; i < P; ++i) CHECK(hb.b.n_tracked[i] == (N >= 15 ? N : 0));
+        std::vector<uint8_t> ref((size_t)(P + 1) * (W + 2) * H, 9), cur((size_t)P * (W + 2) * H, 7);
+        for (int chained = 0; chained < 2; ++chained) {
+            const int row_stride = chained ? W : W + 2;          // whole images in one copy; padded rows, one copy per image
+            dsdtm_stream_desc s{};
+            s.n_pairs = P; s.max_features = N; s.levels = L; s.width = W; s.height = H; s.row_stride = row_stride; s.image_pitch = (size_t)row_stride * H;
+            s.ref_image = ref.data(); s.cur_image = chained ? nullptr : cur.data();
+            s.px_xy = hb.b.px_xy; s.bearing = hb.b.bearing; s.p_world = hb.b.p_world; s.initial = hb.b.initial; s.n_features = hb.b.n_features;
+            s.T_ref_w = hb.b.T_ref_w; s.T_cur_w = hb.b.T_cur_w; s.n_tracked = hb.b.n_tracked; s.stats = hb.b.stats;
+            if (N == 600 && chained) fake_hip_timeout_next(1, 0);    // a chunk is re-run: everything is fetched again
+            CHECK(dsdtm_sparse_align_batch_streamed(one, 1, &s, 2, &cam, &prm) == DSDTM_OK);
+            for (int i = 0; i < P; ++i) CHECK(hb.b.n_tracked[i] == (N >= 15 ? N : 0));
+            CHECK(fake_hip_pending() == 0);
+        }
+    }
+    CHECK(no_fake_errors());
+    dsdtm_destroy(ctx);
+    CHECK(fake_hip_live_allocations() == 0);
+    return true;
+}
+
 // ---- 10. dsdtm_track_frame: the pinned block it packs (image, features, the flattened local map, results) ----
 static bool track_frame_packing() {
     dsdtm_ctx* ctx = nullptr;
@@ -515,15 +701,20 @@ int main(int argc, char** argv) {
         {"recover_slots_past_64", recover_slots_past_64}, {"team_epoch_wrap_is_cleared", team_epoch_wrap_is_cleared},
         {"team_epoch_wrap_hazard_is_real", team_epoch_wrap_hazard_is_real}, {"sharded_refetches_after_rerun", sharded_refetches_after_rerun},
         {"sharded_error_midway", sharded_error_midway}, {"streamed_entry", streamed_entry}, {"frame_lifetime", frame_lifetime},
-        {"single_call_entries", single_call_entries}, {"track_frame_packing", track_frame_packing}, {"track_frame_failures", track_frame_failures},
+        {"single_call_entries", single_call_entries}, {"device_batch_entries", device_batch_entries},
+        {"refused_levels", refused_levels}, {"host_batch_one_context", host_batch_one_context}, {"track_frame_packing", track_frame_packing}, {"track_frame_failures", track_frame_failures},
         {"track_frame_camera_mismatch", track_frame_camera_mismatch}, {"two_contexts_two_threads", two_contexts_two_threads}};
-    int failed = 0;
+    int failed = 0, n_named = 0;
+    bool trace = false;                                // --trace: the call trace behind every scenario (fake_hip_print_trace)
+    for (int i = 1; i < argc; ++i) { if (std::string(argv[i]) == "--trace") trace = true; else n_named += 1; }
     for (const auto& sc : all) {
-        bool wanted = argc < 2;
+        bool wanted = n_named == 0;
         for (int i = 1; i < argc; ++i) wanted = wanted || sc.first == argv[i];
         if (!wanted) continue;
         fake_hip_reset();
+        if (trace) std::printf("== %s\n", sc.first.c_str());
         const bool ok = sc.second();
+        if (trace) fake_hip_print_trace(stdout);      // (what the scenario left behind its last reset)
         std::printf("%s %s\n", ok ? "ok" : "FAILED", sc.first.c_str());
         std::fflush(stdout);
         failed += ok ? 0 : 1;

@@ -17,7 +17,10 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <algorithm>
+#include <set>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "kernels.h"
@@ -42,6 +45,9 @@ std::map<void*, std::pair<size_t, int>> g_mem;      // pointer -> (bytes, hipMem
 std::map<std::string, long> g_calls, g_fail_at;
 std::vector<fake_launch> g_log;
 std::vector<std::string> g_errors;
+struct FakeCopy { fake_stream* s; std::string what; };   // one per copy / memset, in CALL order (fake_hip_print_trace)
+std::vector<FakeCopy> g_copies;
+std::set<std::thread::id> g_threads;                  // the threads that called a counted API since the last reset
 long g_timeout_multi = 0, g_timeout_one = 0, g_kernel_seq = 0;
 int g_next_stream_id = 1;
 
@@ -51,6 +57,7 @@ void fatal(const char* msg) { std::fprintf(stderr, "fake_hip: %s\n", msg); std::
 
 bool should_fail(const char* name) {
     const long n = ++g_calls[name];
+    g_threads.insert(std::this_thread::get_id());
     auto it = g_fail_at.find(name);
     if (it != g_fail_at.end() && it->second == n) { g_fail_at.erase(it); return true; }
     return false;
@@ -89,6 +96,14 @@ void touch_w(void* p, size_t bytes) {
     volatile uint8_t* b = (uint8_t*)p;
     b[0] = b[0]; b[bytes - 1] = b[bytes - 1];
 }
+void note_copy(hipStream_t s, const char* what, int kind, size_t a, size_t b = 0) {
+    static const char* const kinds[] = {"H2H", "H2D", "D2H", "D2D", "default"};
+    char msg[96];
+    if (kind < 0) snprintf(msg, sizeof msg, "%s %zu", what, a);
+    else if (b) snprintf(msg, sizeof msg, "%s %s %zux%zu", what, kinds[kind], a, b);
+    else snprintf(msg, sizeof msg, "%s %s %zu", what, kinds[kind], a);
+    g_copies.push_back(FakeCopy{S(s), msg});          // (NULL: the null stream, as in the launch log; hipMemset counts there too)
+}
 long take(long& counter) { if (counter > 0) { counter--; return 1; } return 0; }
 }  // namespace
 
@@ -98,7 +113,7 @@ long take(long& counter) { if (counter > 0) { counter--; return 1; } return 0; }
 void fake_hip_reset() {
     Lock l(g_mu);
     drain_all_locked();
-    g_calls.clear(); g_fail_at.clear(); g_log.clear(); g_errors.clear();
+    g_calls.clear(); g_fail_at.clear(); g_log.clear(); g_errors.clear(); g_copies.clear(); g_threads.clear();
     g_timeout_multi = g_timeout_one = 0;
 }
 void fake_hip_fail(const char* api, long nth_call_from_now) { Lock l(g_mu); g_fail_at[api] = g_calls[api] + nth_call_from_now; }
@@ -108,6 +123,46 @@ long fake_hip_calls(const char* api) { Lock l(g_mu); return g_calls[api]; }
 std::vector<fake_launch> fake_hip_log() { Lock l(g_mu); return g_log; }
 std::vector<std::string> fake_hip_errors() { Lock l(g_mu); return g_errors; }
 size_t fake_hip_live_allocations() { Lock l(g_mu); return g_mem.size(); }
+// The call trace of everything since the last reset: the number of calls of every counted API, one line per copy / memset (in
+// call order: kind and byte count) and the launch log (in execution order). Streams are numbered by first appearance, execution
+// numbers are relative to the first launch. When more than one thread called in, every stream's own copy and launch sequence is
+// printed instead, sorted: the interleaving differs between two runs of one program.
+void fake_hip_print_trace(FILE* out) {
+    Lock l(g_mu);
+    static const char* const apis[] = {
+        "hipGetDeviceCount", "hipSetDevice", "hipDeviceSynchronize", "hipMalloc", "hipHostMalloc", "hipHostGetDevicePointer", "hipMemset",
+        "hipMemsetAsync", "hipMemcpyAsync", "hipMemcpy2DAsync", "hipStreamCreateWithFlags", "hipStreamSynchronize", "hipEventCreateWithFlags",
+        "hipEventRecord", "hipEventSynchronize", "hipStreamWaitEvent", "sparse_align_launch", "sparse_align_launch_team", "detect_launch",
+        "align2d_launch", "pyrdown_launch", "ingest_launch", "warp_launch", "match_launch", "pose_opt_launch", "track_match_launch",
+        "track_replay_launch"};
+    for (const char* a : apis) { auto it = g_calls.find(a); std::fprintf(out, "calls %s %ld\n", a, it == g_calls.end() ? 0l : it->second); }
+    std::vector<const fake_stream*> order;
+    auto number = [&](const fake_stream* s) {
+        for (size_t i = 0; i < order.size(); ++i) if (order[i] == s) return (int)i;
+        order.push_back(s);
+        return (int)order.size() - 1;
+    };
+    auto kernel = [](const fake_launch& fl) { return fl.kind == FAKE_OTHER ? fl.name : "sa" + std::to_string(fl.kind); };
+    if (g_threads.size() > 1) {
+        for (const fake_launch& fl : g_log) number(S(fl.stream));
+        for (const FakeCopy& c : g_copies) number(c.s);
+        std::vector<std::string> lines;
+        for (const fake_stream* s : order) {
+            std::string seq = "stream-sequence ", cp = "stream-copies ";
+            bool any_seq = false, any_cp = false;
+            for (const fake_launch& fl : g_log) if (S(fl.stream) == s) { seq += kernel(fl) + " "; any_seq = true; }
+            for (const FakeCopy& c : g_copies) if (c.s == s) { cp += c.what + ", "; any_cp = true; }
+            if (any_seq) lines.push_back(seq);
+            if (any_cp) lines.push_back(cp);
+        }
+        std::sort(lines.begin(), lines.end());
+        for (const std::string& ln : lines) std::fprintf(out, "%s\n", ln.c_str());
+        return;
+    }
+    for (const fake_launch& fl : g_log) number(S(fl.stream));
+    for (const FakeCopy& c : g_copies) std::fprintf(out, "%s stream%d\n", c.what.c_str(), number(c.s));
+    for (const fake_launch& fl : g_log) std::fprintf(out, "log %s stream%d seq+%ld\n", kernel(fl).c_str(), number(S(fl.stream)), fl.seq - g_log[0].seq);
+}
 size_t fake_hip_pending() {
     Lock l(g_mu);
     size_t n = g_null_stream.q.size();
@@ -156,22 +211,25 @@ hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void* p) {
         if ((const uint8_t*)p >= (const uint8_t*)kv.first && (const uint8_t*)p < (const uint8_t*)kv.first + kv.second.first) { a->type = (hipMemoryType)kv.second.second; a->device = 0; return hipSuccess; }
     return hipErrorInvalidValue;
 }
-hipError_t hipMemset(void* p, int v, size_t bytes) { FAIL_POINT("hipMemset"); Lock l(g_mu); drain_all_locked(); memset(p, v, bytes); return hipSuccess; }
+hipError_t hipMemset(void* p, int v, size_t bytes) { FAIL_POINT("hipMemset"); Lock l(g_mu); note_copy(nullptr, "memset-sync", -1, bytes); drain_all_locked(); memset(p, v, bytes); return hipSuccess; }
 hipError_t hipMemsetAsync(void* p, int v, size_t bytes, hipStream_t s) {
     FAIL_POINT("hipMemsetAsync");
     Lock l(g_mu);
+    note_copy(s, "memset", -1, bytes);
     enqueue(s, [=]() { memset(p, v, bytes); });
     return hipSuccess;
 }
-hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t s) {
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind k, hipStream_t s) {
     FAIL_POINT("hipMemcpyAsync");
     Lock l(g_mu);
+    note_copy(s, "copy", (int)k, bytes);
     enqueue(s, [=]() { memmove(dst, src, bytes); });
     return hipSuccess;
 }
-hipError_t hipMemcpy2DAsync(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t s) {
+hipError_t hipMemcpy2DAsync(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipMemcpyKind k, hipStream_t s) {
     FAIL_POINT("hipMemcpy2DAsync");
     Lock l(g_mu);
+    note_copy(s, "copy2d", (int)k, width, height);
     enqueue(s, [=]() { for (size_t y = 0; y < height; ++y) memmove((uint8_t*)dst + y * dpitch, (const uint8_t*)src + y * spitch, width); });
     return hipSuccess;
 }

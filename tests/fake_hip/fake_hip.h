@@ -1,5 +1,6 @@
 // tests/fake_hip/fake_hip.h — control interface of the fake HIP runtime (test infrastructure only).
 #pragma once
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -25,3 +26,4 @@ std::vector<fake_launch> fake_hip_log();
 std::vector<std::string> fake_hip_errors();                  // invariant violations seen by the fake kernels
 size_t fake_hip_live_allocations();
 size_t fake_hip_pending();
+void fake_hip_print_trace(FILE* out);                           // call counts, copies / memsets (kind, bytes), launch log since the last reset

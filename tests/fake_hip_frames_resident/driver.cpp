@@ -373,13 +373,17 @@ int main(int argc, char** argv) {
                                                       {"resident_arguments", resident_arguments},
                                                       {"destroy_with_resident_frames", destroy_with_resident_frames},
                                                       {"two_contexts_two_threads", two_contexts_two_threads}};
-    int failed = 0;
+    int failed = 0, n_named = 0;
+    bool trace = false;                                // --trace: the call trace behind every scenario (fake_hip_print_trace)
+    for (int i = 1; i < argc; ++i) { if (std::string(argv[i]) == "--trace") trace = true; else n_named += 1; }
     for (const auto& sc : all) {
-        bool wanted = argc < 2;
+        bool wanted = n_named == 0;
         for (int i = 1; i < argc; ++i) wanted = wanted || sc.first == argv[i];
         if (!wanted) continue;
         fake_hip_reset();
+        if (trace) std::printf("== %s\n", sc.first.c_str());
         const bool ok = sc.second();
+        if (trace) fake_hip_print_trace(stdout);      // (what the scenario left behind its last reset)
         std::printf("%s %s\n", ok ? "ok" : "FAILED", sc.first.c_str());
         std::fflush(stdout);
         failed += ok ? 0 : 1;

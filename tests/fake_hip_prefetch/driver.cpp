@@ -291,9 +291,15 @@ int main(int argc, char** argv) {
         {"destroy_with_a_prefetch_pending", destroy_with_a_prefetch_pending}, {"prefetch_then_track", prefetch_then_track},
         {"two_contexts_two_threads", two_contexts_two_threads}};
     int failed = 0;
+    bool trace = false;                                // --trace: the call trace behind every scenario (fake_hip_print_trace)
+    const char* only = nullptr;
+    for (int i = 1; i < argc; ++i) { if (std::string(argv[i]) == "--trace") trace = true; else if (!only) only = argv[i]; }
     for (auto& t : tests) {
-        if (argc > 1 && std::string(argv[1]) != t.name) continue;
+        if (only && std::string(only) != t.name) continue;
+        fake_hip_reset();
+        if (trace) std::printf("== %s\n", t.name);
         const bool ok = t.fn();
+        if (trace) fake_hip_print_trace(stdout);      // (what the scenario left behind its last reset)
         std::printf("%s %s\n", ok ? "ok" : "FAILED", t.name);
         std::fflush(stdout);
         failed += !ok;

@@ -231,3 +231,182 @@ def test_detector_pyramid_pose_and_sharded_entries(gpu_ctx):
     _refused(gpu_ctx, lib.dsdtm_sparse_align_batch_sharded(two, 1, C.byref(hb), C.byref(cam), C.byref(ap)), "NULL host pointers")
     assert lib.dsdtm_sparse_align_batch_sharded(two, 0, C.byref(hb), C.byref(cam), C.byref(ap)) == capi.ERR_INVALID
     assert lib.dsdtm_sparse_align_batch_sharded(None, 2, C.byref(hb), C.byref(cam), C.byref(ap)) == capi.ERR_INVALID
+
+
+def test_align2d_device_entry_level_table(gpu_ctx, oracle):
+    """dsdtm_align2d_batch_device on a 64x48, 3-level pyramid: a level that ends one byte past the packed pyramid and a level
+    whose rows are shorter than its width are refused with nothing launched (the outputs keep their values); the accepted call
+    then gives the oracle's flags and pixels bit for bit, as tests/test_align2d_gpu.py asks of this entry."""
+    import torch
+    from dsdtm_amd import synth
+    dev = torch.device("cuda", 0)
+    lib, h = gpu_ctx.lib, gpu_ctx.handle
+    pyr = synth.build_pyramid(np.clip(np.rint(synth.make_texture(48, 64, 4)), 0, 255).astype(np.uint8), 3)
+    level = np.array([0, 0, 0, 1], np.int32)
+    centres = [(20.3, 17.6), (40.0, 30.0), (31.5, 24.25), (16.3, 12.2)]
+    pbs, ps = zip(*[[a[0] for a in H.make_border_patches(pyr[l], [c])] for l, c in zip(level, centres)])
+    px0 = np.array(centres) + np.array([[0.7, -0.4], [-1.1, 0.9], [0.2, 0.3], [-0.5, 0.6]])
+    co, pxo = oracle.align2d_batch(pyr, list(pbs), list(ps), level, px0, 10)
+    ws, hs, ss, offs, nb = capi.pyramid_layout(64, 48, 3)
+    packed = np.zeros(nb, np.uint8)
+    for l in range(3):
+        packed[offs[l]:offs[l] + ws[l] * hs[l]] = pyr[l].reshape(-1)
+    d_pyr = torch.from_numpy(packed).to(dev)
+    d_pb, d_p = torch.from_numpy(np.stack(pbs).reshape(4, 100)).to(dev), torch.from_numpy(np.stack(ps).reshape(4, 64)).to(dev)
+    d_px, d_lv = torch.from_numpy(px0.copy()).to(dev), torch.from_numpy(level).to(dev)
+    d_cv = torch.full((4,), 9, dtype=torch.uint8, device=dev)
+    img = capi.ImageDesc()
+    img.levels = 3
+    for l in range(3):
+        img.width[l], img.height[l], img.stride[l], img.level_offset[l] = ws[l], hs[l], ss[l], offs[l]
+    img.bytes, img.data = nb, d_pyr.data_ptr()
+
+    def call(desc):
+        return lib.dsdtm_align2d_batch_device(h, C.byref(desc), d_pb.data_ptr(), d_p.data_ptr(), d_lv.data_ptr(), d_px.data_ptr(),
+                                              d_cv.data_ptr(), 10, 4, None)
+
+    torch.cuda.synchronize()
+    past = _clone(img); past.level_offset[2] = nb - ss[2] * hs[2] + 1
+    _refused(gpu_ctx, call(past), "does not fit")
+    narrow = _clone(img); narrow.stride[1] = ws[1] - 1
+    _refused(gpu_ctx, call(narrow), "does not fit")
+    torch.cuda.synchronize()
+    assert np.array_equal(d_px.cpu().numpy(), px0) and (d_cv.cpu().numpy() == 9).all()      # nothing ran
+    gpu_ctx.check(call(img))
+    torch.cuda.synchronize()
+    assert np.array_equal(d_cv.cpu().numpy().astype(bool), co)
+    assert np.array_equal(d_px.cpu().numpy(), pxo, equal_nan=True)
+
+
+def _tiny_layout():
+    """The packed 64x48, 3-level geometry of the level-table tests, and the two tables that must be refused: the last level
+    ending one byte past the pitch, and a level whose rows are shorter than its width."""
+    ws, hs, ss, offs, nb = capi.pyramid_layout(64, 48, 3)
+    pitch = (nb + 255) // 256 * 256
+    past = list(offs); past[2] = pitch - ss[2] * hs[2] + 1
+    narrow = list(ss); narrow[1] = ws[1] - 1
+    return ws, hs, ss, offs, pitch, past, narrow
+
+
+def _pack(pyr, offs, ws, hs, pitch):
+    out = np.zeros(pitch, np.uint8)
+    for l in range(3):
+        out[offs[l]:offs[l] + ws[l] * hs[l]] = pyr[l].reshape(-1)
+    return out
+
+
+def test_sharded_entry_level_table(gpu_ctx, oracle):
+    """dsdtm_sparse_align_batch_sharded, three 64x48 pairs over two contexts: both bad level tables are refused before any shard
+    starts (the caller's poses and counts keep their values); the accepted call gives the oracle's poses and counts, as
+    tests/test_sharded_gpu.py asks of this entry."""
+    from tests.test_sharded_gpu import _host_batch
+    ws, hs, ss, offs, pitch, past, narrow = _tiny_layout()
+    scenes = [cached_scene(width=64, height=48, levels=3, n_patches=24, seed=9100 + i, margin=10) for i in range(3)]
+    cam = capi.camera_struct(scenes[0].cam)
+    prm = capi.AlignParams(3, 0, 10, 15)
+    a, b, _ = _host_batch(scenes, 3, 64, 48)
+    seed = a["Tc"].copy()
+    ctxs = [capi.Context(0) for _ in range(2)]
+    arr = (C.c_void_p * 2)(*[c.handle for c in ctxs])
+    lib = gpu_ctx.lib
+    bad = _clone(b); bad.level_offset[2] = past[2]
+    _refused(ctxs[0], lib.dsdtm_sparse_align_batch_sharded(arr, 2, C.byref(bad), C.byref(cam), C.byref(prm)), "does not fit")
+    bad = _clone(b); bad.stride[1] = narrow[1]
+    _refused(ctxs[0], lib.dsdtm_sparse_align_batch_sharded(arr, 2, C.byref(bad), C.byref(cam), C.byref(prm)), "does not fit")
+    assert np.array_equal(a["Tc"], seed) and (a["nt"] == -1).all()                          # nothing ran
+    rc = lib.dsdtm_sparse_align_batch_sharded(arr, 2, C.byref(b), C.byref(cam), C.byref(prm))
+    assert rc == 0, ctxs[0].lib.dsdtm_last_error(ctxs[0].handle)
+    for c in ctxs:
+        c.close()
+    for i, sc in enumerate(scenes):
+        To, no, so = oracle.sparse_align(sc, 3, 0, 10)
+        H.assert_pose_close(a["Tc"][i].reshape(3, 4), To, H.TIGHT_RAD * 10, H.TIGHT_M * 10, what=f"pair {i}")
+        assert a["nt"][i] == no and no >= 15 and list(a["st"]["iters"][i][:3]) == list(so["iters"][:3])
+
+
+def test_detector_batch_entry_level_table(gpu_ctx, oracle):
+    """dsdtm_detect_cells_batch_device, two 64x48 frames: both bad level tables are refused with nothing enqueued (the outputs keep
+    their values); the accepted call gives the oracle's cells frame by frame, as tests/test_detector_gpu.py asks of this entry."""
+    import torch
+    from dsdtm_amd import synth
+    dev = torch.device("cuda", 0)
+    ws, hs, ss, offs, pitch, past, narrow = _tiny_layout()
+    pyrs = [synth.build_pyramid(np.clip(np.rint(synth.make_texture(48, 64, 300 + i)), 0, 255).astype(np.uint8), 3) for i in range(2)]
+    G = 8 * 6
+    occ = np.zeros((2, G), np.uint8); occ[:, 5] = 1
+    prm = capi.DetectParams(8, 8, 6, 3, 20, 5.0)
+    d_pyr = torch.from_numpy(np.stack([_pack(p, offs, ws, hs, pitch) for p in pyrs])).to(dev)
+    d_occ = torch.from_numpy(occ).to(dev)
+    d_score = torch.zeros((2, pitch), dtype=torch.uint8, device=dev)
+    d_key = torch.zeros((2, G), dtype=torch.int64, device=dev)
+    d_s = torch.full((2, G), -7.0, dtype=torch.float32, device=dev)
+    d_x, d_y, d_l = (torch.full((2, G), -7, dtype=torch.int32, device=dev) for _ in range(3))
+    ia = lambda v: (C.c_int * 3)(*v)
+
+    def call(st=ss, of=offs):
+        return gpu_ctx.lib.dsdtm_detect_cells_batch_device(gpu_ctx.handle, d_pyr.data_ptr(), pitch, 2, 3, ia(ws), ia(hs), ia(st), (C.c_size_t * 3)(*of),
+                                                           d_occ.data_ptr(), C.byref(prm), d_score.data_ptr(), d_key.data_ptr(), d_s.data_ptr(),
+                                                           d_x.data_ptr(), d_y.data_ptr(), d_l.data_ptr(), None)
+
+    torch.cuda.synchronize()
+    _refused(gpu_ctx, call(of=past), "does not fit")
+    _refused(gpu_ctx, call(st=narrow), "does not fit")
+    torch.cuda.synchronize()
+    assert (d_s.cpu().numpy() == -7.0).all() and (d_l.cpu().numpy() == -7).all()           # nothing ran
+    gpu_ctx.check(call())
+    torch.cuda.synchronize()
+    got = [t.cpu().numpy() for t in (d_s, d_x, d_y, d_l)]
+    for i in range(2):
+        want = oracle.detect_cells(pyrs[i], 3, 8, 8, 6, occ[i], 5.0)
+        for g, wv, name in zip(got, want, ("score", "x", "y", "level")):
+            assert np.array_equal(g[i], wv), (i, name)
+        assert (got[0][i] > 5.0).sum() > 20
+
+
+def test_match_candidates_batch_entry_level_table(gpu_ctx, oracle):
+    """dsdtm_match_candidates_batch_device, two 64x48 current frames, one keyframe, four candidates: both bad level tables are
+    refused with nothing enqueued (pixels, levels and flags keep their values); the accepted call gives the oracle's warp prelude
+    + Align2D bit for bit, the comparison of tools/soak_fmd.py."""
+    import torch
+    from tests import oracle_lib
+    dev = torch.device("cuda", 0)
+    ws, hs, ss, offs, pitch, past, narrow = _tiny_layout()
+    sc = cached_scene(width=64, height=48, levels=3, n_patches=24, seed=9100, margin=10)
+    cam = sc.cam
+    curs, Tc = [sc.cur_pyr, sc.ref_pyr], np.stack([sc.T_cur_w_true.reshape(12), sc.T_ref_w.reshape(12)])   # frame 1: the keyframe itself
+    Tk = np.ascontiguousarray(sc.T_ref_w.reshape(1, 12))
+    fr, kf, rl = np.array([0, 0, 1, 1], np.int32), np.zeros(4, np.int32), np.array([0, 1, 0, 1], np.int32)
+    rp, rb, pw = np.ascontiguousarray(sc.px[:4], np.float32), np.ascontiguousarray(sc.bearing[:4]), np.ascontiguousarray(sc.p_world[:4])
+    T = Tc[fr].reshape(4, 3, 4)
+    Xc = np.einsum("mij,mj->mi", T[:, :, :3], pw) + T[:, :, 3]
+    cpx = np.stack([cam.fx * Xc[:, 0] / Xc[:, 2] + cam.cx, cam.fy * Xc[:, 1] / Xc[:, 2] + cam.cy], 1) + np.array([[0.4, -0.3], [-0.6, 0.5], [0.2, 0.7], [-0.5, -0.4]])
+    t = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+    d_cur, d_kf = t(np.stack([_pack(p, offs, ws, hs, pitch) for p in curs])), t(_pack(sc.ref_pyr, offs, ws, hs, pitch))
+    d_Tk, d_Tc, d_fr, d_ck, d_rp, d_rl, d_rb, d_pw = t(Tk), t(Tc), t(fr), t(kf), t(rp), t(rl), t(rb), t(pw)
+    d_px = t(cpx.copy())
+    d_sl, d_cv = torch.full((4,), 7, dtype=torch.int32, device=dev), torch.full((4,), 9, dtype=torch.uint8, device=dev)
+    d_scr = torch.zeros(gpu_ctx.lib.dsdtm_match_candidates_scratch_bytes(4), dtype=torch.uint8, device=dev)
+    cs = capi.camera_struct(cam)
+    ia = lambda v: (C.c_int * 3)(*v)
+
+    def call(st=ss, of=offs):
+        return gpu_ctx.lib.dsdtm_match_candidates_batch_device(
+            gpu_ctx.handle, d_cur.data_ptr(), 2, d_kf.data_ptr(), 1, pitch, 3, ia(ws), ia(hs), ia(st), (C.c_size_t * 3)(*of), C.byref(cs),
+            d_Tk.data_ptr(), d_Tc.data_ptr(), d_fr.data_ptr(), d_ck.data_ptr(), d_rp.data_ptr(), d_rl.data_ptr(), d_rb.data_ptr(), d_pw.data_ptr(),
+            0, 10, 4, d_scr.data_ptr(), d_px.data_ptr(), d_sl.data_ptr(), d_cv.data_ptr(), None)
+
+    torch.cuda.synchronize()
+    _refused(gpu_ctx, call(of=past), "does not fit")
+    _refused(gpu_ctx, call(st=narrow), "does not fit")
+    torch.cuda.synchronize()
+    assert np.array_equal(d_px.cpu().numpy(), cpx) and (d_sl.cpu().numpy() == 7).all() and (d_cv.cpu().numpy() == 9).all()   # nothing ran
+    gpu_ctx.check(call())
+    torch.cuda.synchronize()
+    g_px, g_sl, g_cv = d_px.cpu().numpy(), d_sl.cpu().numpy(), d_cv.cpu().numpy().astype(bool)
+    for f in range(2):
+        sel = np.nonzero(fr == f)[0]
+        aff, sl, pb, pp = oracle_lib.warp_patches([sc.ref_pyr], cam, Tk.reshape(1, 3, 4), Tc[f].reshape(3, 4), kf[sel], rp[sel], rl[sel], rb[sel], pw[sel], 0)
+        cv, px = oracle_lib.align2d_batch(curs[f], pb, pp, sl, cpx[sel] / (1 << sl)[:, None], 10)
+        assert np.array_equal(g_sl[sel], sl) and np.array_equal(g_cv[sel], cv)
+        assert np.array_equal(g_px[sel], px * (1 << sl)[:, None], equal_nan=True)
+    assert g_cv.any()
