@@ -35,6 +35,10 @@ KEYFRAME_SOURCES = ["keyframe_api.cpp", "keyframe.hip"]
 KEYFRAME_HEADERS = ["keyframe.h", "device_math.h", "pose_math.h", "exports.map", os.path.join("..", "..", "include", "dsdtm_amd_keyframe.h"),
                     os.path.join("..", "..", "include", "dsdtm_amd.h")]
 OUT_KEYFRAME = os.path.join(HERE, "libdsdtm_amd_keyframe.so")
+# the second add-on (include/dsdtm_amd_motion.h: the moving-object mask of Tracking::MotionRemoval), on the same terms
+MOTION_SOURCES = ["motion_api.cpp", "motion.hip"]
+MOTION_HEADERS = ["motion.h", "exports.map", os.path.join("..", "..", "include", "dsdtm_amd_motion.h"), os.path.join("..", "..", "include", "dsdtm_amd.h")]
+OUT_MOTION = os.path.join(HERE, "libdsdtm_amd_motion.so")
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")
 TAG = OUT + ".tag"
@@ -130,28 +134,39 @@ def build(force=False, verbose=True, extra=(), diag=False):
     return out
 
 
-def build_keyframe(force=False, verbose=True):
-    """libdsdtm_amd_keyframe.so: the add-on's two sources, each to its own object, linked through the same version script."""
+def _build_addon(sources, headers, out, force, verbose):
+    """An add-on library: its sources, each to its own object with the release flags, linked through the same version script."""
     flags = _flags([])
     hipcc = os.environ.get("HIPCC", "hipcc")
-    hdrs = [os.path.join(HERE, h) for h in KEYFRAME_HEADERS] + [os.path.abspath(__file__)]
+    hdrs = [os.path.join(HERE, h) for h in headers] + [os.path.abspath(__file__)]
     os.makedirs(OBJ_DIR, exist_ok=True)
-    objs = [_obj(s, flags) for s in KEYFRAME_SOURCES]
-    jobs = [[hipcc, *flags, "-x", "hip", "-c", os.path.join(HERE, s), "-o", o] for s, o in zip(KEYFRAME_SOURCES, objs)
+    objs = [_obj(s, flags) for s in sources]
+    jobs = [[hipcc, *flags, "-x", "hip", "-c", os.path.join(HERE, s), "-o", o] for s, o in zip(sources, objs)
             if force or _stale(o, [os.path.join(HERE, s)] + hdrs)]
-    if not jobs and not _stale(OUT_KEYFRAME, objs) and not force:
-        return OUT_KEYFRAME
+    if not jobs and not _stale(out, objs) and not force:
+        return out
     for cmd in jobs + [[hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-fno-gpu-rdc",
-                        "-Wl,--version-script=" + os.path.join(HERE, "exports.map"), *objs, "-o", OUT_KEYFRAME]]:
+                        "-Wl,--version-script=" + os.path.join(HERE, "exports.map"), *objs, "-o", out]]:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True, cwd=HERE)
-    return OUT_KEYFRAME
+    return out
+
+
+def build_keyframe(force=False, verbose=True):
+    """libdsdtm_amd_keyframe.so: the add-on's two sources, each to its own object, linked through the same version script."""
+    return _build_addon(KEYFRAME_SOURCES, KEYFRAME_HEADERS, OUT_KEYFRAME, force, verbose)
+
+
+def build_motion(force=False, verbose=True):
+    """libdsdtm_amd_motion.so: the same for the motion-mask add-on."""
+    return _build_addon(MOTION_SOURCES, MOTION_HEADERS, OUT_MOTION, force, verbose)
 
 
 def build_all(force=False, verbose=True):
-    """The release library and the diagnostic one (what __graft_entry__.build() and the test session build), and the add-on."""
+    """The release library and the diagnostic one (what __graft_entry__.build() and the test session build), and the two add-ons."""
     build_keyframe(force, verbose)
+    build_motion(force, verbose)
     return build(force, verbose), build(force, verbose, diag=True)
 
 
@@ -170,3 +185,4 @@ if __name__ == "__main__":
         print(build(a.force, extra=extra, diag=True))
     if a.all:
         print(build_keyframe(a.force))
+        print(build_motion(a.force))
