@@ -50,8 +50,8 @@ __device__ __forceinline__ void fast10_extrema(const T* d, T& best_min, T& worst
 }
 
 // ---- one thread per pixel: levels whose width is not a multiple of 4 ---------------------------------------------
-// (grid: x = pixel columns of level 0 / 256, y = rows of level 0, z = frame * levels + level; blocks outside a smaller
-// level leave at once)
+// (grid: x = pixel columns of the widest such level / 256, y = rows of the tallest one, z = frame * levels + level; blocks
+// outside a smaller level leave at once)
 __global__ __launch_bounds__(256) void fast_score_kernel(const DetectArgs a, unsigned level_mask) {
     const int level = blockIdx.z % a.levels, frame = blockIdx.z / a.levels;
     if (!((level_mask >> level) & 1u)) return;
@@ -436,17 +436,18 @@ hipError_t detect_launch(const DetectArgs& a, hipStream_t stream) {
     if (a.n_frames <= 0) return hipSuccess;
     // levels whose rows are whole dwords take the strip kernel, the others (odd widths) one thread per pixel
     unsigned strip_mask = 0, pixel_mask = 0;
-    int strip_tasks = 0;
+    // (both grids are as large as the largest of their levels needs: the batch entry takes any level table, level 0 need not be it)
+    int strip_tasks = 0, pixel_w = 0, pixel_h = 0;
     for (int l = 0; l < a.levels; ++l) {
         const bool strip = ((a.lv[l].w | a.lv[l].stride | (int)a.lv[l].off) & 3) == 0 && a.lv[l].w >= 16 && (a.pyr_pitch & 3) == 0;
         if (strip) { strip_mask |= 1u << l; const int t = (a.lv[l].w >> 2) * ((a.lv[l].h + FS_ROWS - 1) / FS_ROWS); strip_tasks = t > strip_tasks ? t : strip_tasks; }
-        else pixel_mask |= 1u << l;
+        else { pixel_mask |= 1u << l; pixel_w = a.lv[l].w > pixel_w ? a.lv[l].w : pixel_w; pixel_h = a.lv[l].h > pixel_h ? a.lv[l].h : pixel_h; }
     }
     if (strip_mask)
         hipLaunchKernelGGL(fast_score_strip_kernel, dim3((unsigned)((strip_tasks + 255) / 256), (unsigned)a.levels, (unsigned)a.n_frames),
                            dim3(256), 0, stream, a, strip_mask);
     if (pixel_mask)
-        hipLaunchKernelGGL(fast_score_kernel, dim3((unsigned)((a.lv[0].w + 255) / 256), (unsigned)a.lv[0].h, (unsigned)(a.levels * a.n_frames)),
+        hipLaunchKernelGGL(fast_score_kernel, dim3((unsigned)((pixel_w + 255) / 256), (unsigned)pixel_h, (unsigned)(a.levels * a.n_frames)),
                            dim3(256), 0, stream, a, pixel_mask);
     const int px = a.n_frames >= 8 ? 4 : 1;
     if (px == 4 && pixel_mask == 0) {
