@@ -11,6 +11,8 @@ import os
 
 import numpy as np
 
+from . import _addon
+
 MAX_LEVELS = 8
 OK, ERR_NO_DEVICE, ERR_INVALID, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3, -4
 
@@ -454,64 +456,27 @@ def track_frames(ctx, cam, n, descs, results, matches, residual_norm, in_grid, f
 
 
 def keyframe_lib_path() -> str:
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", KEYFRAME_LIB_NAME)
+    return _addon.lib_path(KEYFRAME_LIB_NAME)
+
+
+def _keyframe_not_built(path):
+    return ImportError(f"{path} not found: the HIP extension is not built. Run "
+                       "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). dsdtm_amd has no CPU fallback.")
 
 
 def load_keyframe():
     """Load libdsdtm_amd_keyframe.so (include/dsdtm_amd_keyframe.h). No fallback: raises if it has not been built."""
-    if "keyframe" in _LIBS:
-        return _LIBS["keyframe"]
-    path = keyframe_lib_path()
-    if not os.path.exists(path):
-        raise ImportError(f"{path} not found: the HIP extension is not built. Run "
-                          "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). dsdtm_amd has no CPU fallback.")
-    lib = C.CDLL(path)
-    lib.dsdtm_keyframe_create.restype = C.c_int
-    lib.dsdtm_keyframe_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    lib.dsdtm_keyframe_destroy.restype = None
-    lib.dsdtm_keyframe_destroy.argtypes = [C.c_void_p]
-    lib.dsdtm_keyframe_last_error.restype = C.c_char_p
-    lib.dsdtm_keyframe_last_error.argtypes = [C.c_void_p]
-    lib.dsdtm_need_keyframe.restype = C.c_int
-    lib.dsdtm_need_keyframe.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(KeyframeParams), C.POINTER(KeyframeDesc), C.c_void_p]
-    lib.dsdtm_need_keyframes.restype = C.c_int
-    lib.dsdtm_need_keyframes.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(KeyframeParams), C.c_int, C.POINTER(KeyframeDesc),
-                                         C.c_void_p]
-    _LIBS["keyframe"] = lib
-    return lib
+    vp, i = C.c_void_p, C.c_int
+    return _addon.load_addon(KEYFRAME_LIB_NAME, {
+        **_addon.context_signatures("dsdtm_keyframe"),
+        "dsdtm_need_keyframe": (i, [vp, C.POINTER(Camera), C.POINTER(KeyframeParams), C.POINTER(KeyframeDesc), vp]),
+        "dsdtm_need_keyframes": (i, [vp, C.POINTER(Camera), C.POINTER(KeyframeParams), i, C.POINTER(KeyframeDesc), vp])},
+        _keyframe_not_built)
 
 
-class KeyframeContext:
+class KeyframeContext(_addon.AddonContext):
     """A dsdtm_keyframe_ctx: the add-on library's own context (stream + staging block) on one device."""
-
-    def __init__(self, device: int = 0):
-        self.lib = load_keyframe()
-        self.device = device
-        h = C.c_void_p()
-        st = self.lib.dsdtm_keyframe_create(device, C.byref(h))
-        if st != OK:
-            msg = self.lib.dsdtm_keyframe_last_error(None)
-            raise DsdtmError(st, msg.decode() if msg else "")
-        self.handle = h
-
-    def last_error(self) -> str:
-        msg = self.lib.dsdtm_keyframe_last_error(self.handle)
-        return msg.decode() if msg else ""
-
-    def check(self, st: int):
-        if st != OK:
-            raise DsdtmError(st, self.last_error())
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.dsdtm_keyframe_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, ERROR, load = "dsdtm_keyframe", DsdtmError, staticmethod(load_keyframe)
 
 
 def keyframe_context_of(ctx) -> KeyframeContext:

@@ -2,7 +2,7 @@
 
     python dsdtm_amd/csrc/build.py            # the RELEASE library  libdsdtm_amd.so       (the product)
     python dsdtm_amd/csrc/build.py --diag     # the DIAGNOSTIC build libdsdtm_amd_diag.so  (tools/, diag-marked tests)
-    python dsdtm_amd/csrc/build.py --all      # both
+    python dsdtm_amd/csrc/build.py --all      # both, and the add-on libraries (the ADDONS table)
     ... [--force] [--define X=1 ...] [--flag F ...]   (extra flags: experiments, see below)
 
 RELEASE (default): exports exactly the symbols include/dsdtm_amd.h declares (linker version script exports.map), reads no
@@ -16,7 +16,8 @@ paths they replaced).
 Every source is compiled to its own object under csrc/build/ (only when it or a header is newer; in parallel; objects are
 keyed by the flag set), then linked: a change to one kernel file recompiles that file only. The flag set a library was
 linked from is recorded beside it (<lib>.tag): a request for another flag set relinks even when every object is fresh, so an
-experiment build (--define / --flag) can never be mistaken for the default one.
+experiment build (--define / --flag) can never be mistaken for the default one. The add-on libraries (the ADDONS table) go
+through the same routine, with the release flags.
 """
 import argparse
 import concurrent.futures
@@ -29,16 +30,21 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["api.cpp", "sparse_align.hip", "align2d.hip", "pyrdown.hip", "warp.hip", "match.hip", "detect.hip", "pose_opt.hip", "track.hip", "local_ba.hip", "rgbd.hip"]
 DIAG_SOURCES = ["selftest.hip"]                      # diagnostic build only
 HEADERS = ["kernels.h", "device_math.h", "warp_body.h", "align2d_body.h", "match_body.h", "pose_math.h", "exports.map", os.path.join("..", "..", "include", "dsdtm_amd.h")]
-# the add-on library (include/dsdtm_amd_keyframe.h: Tracking::NeedKeyframe for n trackers): sources and headers of its own, so that
-# libdsdtm_amd.so — its symbols, its source hash — is untouched by it; built by build_all() with the release flags
-KEYFRAME_SOURCES = ["keyframe_api.cpp", "keyframe.hip"]
-KEYFRAME_HEADERS = ["keyframe.h", "device_math.h", "pose_math.h", "exports.map", os.path.join("..", "..", "include", "dsdtm_amd_keyframe.h"),
-                    os.path.join("..", "..", "include", "dsdtm_amd.h")]
 OUT_KEYFRAME = os.path.join(HERE, "libdsdtm_amd_keyframe.so")
-# the second add-on (include/dsdtm_amd_motion.h: the moving-object mask of Tracking::MotionRemoval), on the same terms
-MOTION_SOURCES = ["motion_api.cpp", "motion.hip"]
-MOTION_HEADERS = ["motion.h", "exports.map", os.path.join("..", "..", "include", "dsdtm_amd_motion.h"), os.path.join("..", "..", "include", "dsdtm_amd.h")]
 OUT_MOTION = os.path.join(HERE, "libdsdtm_amd_motion.so")
+_INC = os.path.join("..", "..", "include")
+# The add-on libraries: name -> (sources, headers, output). Each has sources and headers of its own (the host scaffold addon_host.h is
+# shared among them), so that libdsdtm_amd.so, its symbols and its source hash, is untouched by them; built with the release flags by
+# build_all() and --all. A new add-on is a new row.
+ADDONS = {
+    # include/dsdtm_amd_keyframe.h: Tracking::NeedKeyframe for n trackers
+    "keyframe": (["keyframe_api.cpp", "keyframe.hip"],
+                 ["keyframe.h", "addon_host.h", "device_math.h", "pose_math.h", "exports.map", os.path.join(_INC, "dsdtm_amd_keyframe.h"),
+                  os.path.join(_INC, "dsdtm_amd.h")], OUT_KEYFRAME),
+    # include/dsdtm_amd_motion.h: the moving-object mask of Tracking::MotionRemoval
+    "motion": (["motion_api.cpp", "motion.hip"],
+               ["motion.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_motion.h"), os.path.join(_INC, "dsdtm_amd.h")], OUT_MOTION),
+}
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")
 TAG = OUT + ".tag"
@@ -91,31 +97,27 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def needs_build(extra=(), diag=False):
-    flags = _flags(list(extra), diag)
-    out = out_path(diag)
-    hdrs = [os.path.join(HERE, h) for h in HEADERS] + [os.path.abspath(__file__)]
-    srcs = _sources(diag)
-    objs = [_obj(s, flags) for s in srcs]
-    return (_linked_tag(out) != _tag(flags) or _stale(out, objs)
-            or any(_stale(o, [os.path.join(HERE, s)] + hdrs) for o, s in zip(objs, srcs)))
+def _plan(sources, headers, flags):
+    """(object, what it depends on) per source."""
+    hdrs = [os.path.join(HERE, h) for h in headers] + [os.path.abspath(__file__)]
+    return [(_obj(s, flags), [os.path.join(HERE, s)] + hdrs) for s in sources]
 
 
-def build(force=False, verbose=True, extra=(), diag=False):
-    flags = _flags(list(extra), diag)
-    out = out_path(diag)
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    hdrs = [os.path.join(HERE, h) for h in HEADERS] + [os.path.abspath(__file__)]
-    os.makedirs(OBJ_DIR, exist_ok=True)
-    srcs = _sources(diag)
-    jobs = []
-    for s in srcs:
-        o = _obj(s, flags)
-        if force or _stale(o, [os.path.join(HERE, s)] + hdrs):
-            jobs.append([hipcc, *flags, "-x", "hip", "-c", os.path.join(HERE, s), "-o", o])
-    objs = [_obj(s, flags) for s in srcs]
-    if not jobs and not _stale(out, objs) and not force and _linked_tag(out) == _tag(flags):
+def _needs(sources, headers, out, flags):
+    plan = _plan(sources, headers, flags)
+    # (the objects first: one that is missing is stale, and has no time to hold the library's against)
+    return (any(_stale(o, deps) for o, deps in plan) or _linked_tag(out) != _tag(flags) or _stale(out, [o for o, _ in plan]))
+
+
+def _make(sources, headers, out, flags, force, verbose):
+    """THE compile-and-link routine of every library here: each stale source to its own object (in parallel), then, if anything was
+    compiled, the library is older than an object or its tag is not this flag set's, the link through exports.map and the tag."""
+    if not force and not _needs(sources, headers, out, flags):
         return out
+    hipcc = os.environ.get("HIPCC", "hipcc")
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    plan = _plan(sources, headers, flags)
+    jobs = [[hipcc, *flags, "-x", "hip", "-c", deps[0], "-o", o] for o, deps in plan if force or _stale(o, deps)]
 
     def run(cmd):
         if verbose:
@@ -126,47 +128,45 @@ def build(force=False, verbose=True, extra=(), diag=False):
     tag = out + ".tag"
     if os.path.exists(tag):
         os.remove(tag)          # no tag while the library is being replaced
-    # exports.map: only dsdtm_* leaves the library (release: exactly the header's symbols; diag: + dsdtm_debug_*)
+    # exports.map: only dsdtm_* leaves a library (release: exactly the header's symbols; diag: + dsdtm_debug_*)
     run([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-fno-gpu-rdc", "-Wl,--version-script=" + os.path.join(HERE, "exports.map"),
-         *objs, "-o", out])
+         *[o for o, _ in plan], "-o", out])
     with open(tag, "w") as f:
         f.write(_tag(flags) + "\n")
     return out
 
 
-def _build_addon(sources, headers, out, force, verbose):
-    """An add-on library: its sources, each to its own object with the release flags, linked through the same version script."""
-    flags = _flags([])
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    hdrs = [os.path.join(HERE, h) for h in headers] + [os.path.abspath(__file__)]
-    os.makedirs(OBJ_DIR, exist_ok=True)
-    objs = [_obj(s, flags) for s in sources]
-    jobs = [[hipcc, *flags, "-x", "hip", "-c", os.path.join(HERE, s), "-o", o] for s, o in zip(sources, objs)
-            if force or _stale(o, [os.path.join(HERE, s)] + hdrs)]
-    if not jobs and not _stale(out, objs) and not force:
-        return out
-    for cmd in jobs + [[hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-fno-gpu-rdc",
-                        "-Wl,--version-script=" + os.path.join(HERE, "exports.map"), *objs, "-o", out]]:
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True, cwd=HERE)
-    return out
+def needs_build(extra=(), diag=False):
+    return _needs(_sources(diag), HEADERS, out_path(diag), _flags(list(extra), diag))
+
+
+def build(force=False, verbose=True, extra=(), diag=False):
+    return _make(_sources(diag), HEADERS, out_path(diag), _flags(list(extra), diag), force, verbose)
+
+
+def addon_needs_build(name):
+    sources, headers, out = ADDONS[name]
+    return _needs(sources, headers, out, _flags([]))
+
+
+def build_addon(name, force=False, verbose=True):
+    """An add-on library of the table above, with the release flags."""
+    sources, headers, out = ADDONS[name]
+    return _make(sources, headers, out, _flags([]), force, verbose)
 
 
 def build_keyframe(force=False, verbose=True):
-    """libdsdtm_amd_keyframe.so: the add-on's two sources, each to its own object, linked through the same version script."""
-    return _build_addon(KEYFRAME_SOURCES, KEYFRAME_HEADERS, OUT_KEYFRAME, force, verbose)
+    return build_addon("keyframe", force, verbose)
 
 
 def build_motion(force=False, verbose=True):
-    """libdsdtm_amd_motion.so: the same for the motion-mask add-on."""
-    return _build_addon(MOTION_SOURCES, MOTION_HEADERS, OUT_MOTION, force, verbose)
+    return build_addon("motion", force, verbose)
 
 
 def build_all(force=False, verbose=True):
-    """The release library and the diagnostic one (what __graft_entry__.build() and the test session build), and the two add-ons."""
-    build_keyframe(force, verbose)
-    build_motion(force, verbose)
+    """The release library and the diagnostic one (what __graft_entry__.build() and the test session build), and every add-on."""
+    for name in ADDONS:
+        build_addon(name, force, verbose)
     return build(force, verbose), build(force, verbose, diag=True)
 
 
@@ -174,7 +174,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
     ap.add_argument("--diag", action="store_true", help="build libdsdtm_amd_diag.so (debug entries, environment switches, superseded kernels)")
-    ap.add_argument("--all", action="store_true", help="build both libraries")
+    ap.add_argument("--all", action="store_true", help="build both libraries and every add-on")
     ap.add_argument("--define", action="append", default=[], help="extra -D for experiments")
     ap.add_argument("--flag", action="append", default=[], help="extra raw compiler flag for experiments, e.g. --flag=-mllvm --flag=-amdgpu-sched-strategy=max-ilp")
     a = ap.parse_args()
@@ -184,5 +184,5 @@ if __name__ == "__main__":
     if a.all or a.diag:
         print(build(a.force, extra=extra, diag=True))
     if a.all:
-        print(build_keyframe(a.force))
-        print(build_motion(a.force))
+        for name in ADDONS:
+            print(build_addon(name, a.force))

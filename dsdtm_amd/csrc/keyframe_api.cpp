@@ -1,4 +1,4 @@
-// keyframe_api.cpp — the C ABI of include/dsdtm_amd_keyframe.h (libdsdtm_amd_keyframe.so): context, checks, packing, launch.
+// keyframe_api.cpp — the C ABI of include/dsdtm_amd_keyframe.h (libdsdtm_amd_keyframe.so): checks, packing, launch (the context: addon_host.h).
 //
 // The add-on's one entry packs the n trackers into one pinned blob, moves it with a single hipMemcpyAsync, launches
 // keyframe.hip's kernel on the context's stream and copies the n verdicts back. There is no CPU compute path here (the host
@@ -6,110 +6,19 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "keyframe.h"
+#include "addon_host.h"
 
 using namespace dsdtm;
 
-struct dsdtm_keyframe_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    char err[512] = {0};
-    void* h_pinned = nullptr;      // staging: the blob and the verdicts as the host sees them ...
-    size_t h_cap = 0;
-    void* d_stage = nullptr;       // ... and on the device
-    size_t d_cap = 0;
-};
+struct dsdtm_keyframe_ctx : dsdtm::AddonCtx {};      // (staging: the blob and the verdicts, at the same offsets on both sides)
 
-static thread_local char g_create_err[512] = "";
-
-static void set_err(dsdtm_keyframe_ctx* ctx, const char* fmt, ...) {
-    char* dst = ctx ? ctx->err : g_create_err;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(dst, 512, fmt, ap);
-    va_end(ap);
-}
-
-#define HIP_TRY(ctx, call)                                                                   \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return DSDTM_ERR_HIP;                                                            \
-        }                                                                                    \
-    } while (0)
-// HIP_TRY behind the first enqueue: answered by the enclosing `fail` lambda (which waits for what was enqueued)
-#define API_TRY(call)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
-    } while (0)
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-extern "C" const char* dsdtm_keyframe_last_error(const dsdtm_keyframe_ctx* ctx) { return ctx ? ctx->err : g_create_err; }
-
-extern "C" int dsdtm_keyframe_create(int device, dsdtm_keyframe_ctx** out) {
-    if (!out) return DSDTM_ERR_INVALID;
-    *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-        set_err(nullptr, "no HIP device visible (%s); dsdtm_amd_keyframe has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-        return DSDTM_ERR_NO_DEVICE;
-    }
-    if (device < 0 || device >= n) { set_err(nullptr, "device %d out of range (%d visible)", device, n); return DSDTM_ERR_NO_DEVICE; }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { set_err(nullptr, "hipGetDeviceProperties(%d) failed", device); return DSDTM_ERR_NO_DEVICE; }
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_err(nullptr, "device %d is %s; this library contains gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return DSDTM_ERR_NO_DEVICE;
-    }
-    dsdtm_keyframe_ctx* ctx = new (std::nothrow) dsdtm_keyframe_ctx();
-    if (!ctx) return DSDTM_ERR_NOMEM;
-    ctx->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_err(nullptr, "hipSetDevice/hipStreamCreate failed on device %d", device);
-        delete ctx;
-        return DSDTM_ERR_HIP;
-    }
-    *out = ctx;
-    return DSDTM_OK;
-}
-
-extern "C" void dsdtm_keyframe_destroy(dsdtm_keyframe_ctx* ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); (void)hipStreamDestroy(ctx->stream); }
-    if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-    delete ctx;
-}
-
-static int ensure_stage(dsdtm_keyframe_ctx* ctx, size_t bytes) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (bytes > ctx->h_cap) {
-        if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-        ctx->h_pinned = nullptr; ctx->h_cap = 0;
-        const size_t cap = align_up(bytes + bytes / 4, 1 << 16);
-        HIP_TRY(ctx, hipHostMalloc(&ctx->h_pinned, cap, hipHostMallocDefault));
-        ctx->h_cap = cap;
-    }
-    if (bytes > ctx->d_cap) {
-        if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-        ctx->d_stage = nullptr; ctx->d_cap = 0;
-        const size_t cap = align_up(bytes + bytes / 4, 1 << 16);
-        HIP_TRY(ctx, hipMalloc(&ctx->d_stage, cap));
-        ctx->d_cap = cap;
-    }
-    return DSDTM_OK;
-}
+extern "C" const char* dsdtm_keyframe_last_error(const dsdtm_keyframe_ctx* ctx) { return addon_last_error(ctx); }
+extern "C" int dsdtm_keyframe_create(int device, dsdtm_keyframe_ctx** out) { return addon_create("dsdtm_amd_keyframe", device, out); }
+extern "C" void dsdtm_keyframe_destroy(dsdtm_keyframe_ctx* ctx) { addon_destroy(ctx); }
 
 static bool all_finite(const double* v, size_t n) {
     for (size_t i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false;
@@ -157,7 +66,7 @@ extern "C" int dsdtm_need_keyframes(dsdtm_keyframe_ctx* ctx, const dsdtm_camera*
         r.lkf = o; o += align_up((size_t)d.n_local_kf * 24, 16);
     }
     const size_t blob = align_up(o, 256), vbytes = N * sizeof(dsdtm_keyframe_verdict);
-    if (int rc = ensure_stage(ctx, blob + vbytes)) return rc;
+    if (int rc = ensure_stage(ctx, blob + vbytes, blob + vbytes)) return rc;
     uint8_t* h = (uint8_t*)ctx->h_pinned;
     uint8_t* g = (uint8_t*)ctx->d_stage;
     memcpy(h, rec.data(), N * sizeof(KeyframeTrackerDev));

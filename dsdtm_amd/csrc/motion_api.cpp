@@ -1,4 +1,4 @@
-// motion_api.cpp — the C ABI of include/dsdtm_amd_motion.h (libdsdtm_amd_motion.so): context, models, checks, packing, launch.
+// motion_api.cpp — the C ABI of include/dsdtm_amd_motion.h (libdsdtm_amd_motion.so): models, checks, packing, launch (the context: addon_host.h).
 //
 // A step packs the n models' records, host images and feature coordinates into one pinned block, moves it with a single
 // hipMemcpyAsync, launches motion.hip's step kernel (and, where features were given, the lookup behind it) on the context's stream
@@ -8,25 +8,18 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "motion.h"
+#include "addon_host.h"
 
 using namespace dsdtm;
 
-struct dsdtm_motion_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    char err[512] = {0};
-    void* h_pinned = nullptr;      // staging as the host sees it ...
-    size_t h_cap = 0;
-    void* d_stage = nullptr;       // ... and on the device (same offsets)
-    size_t d_cap = 0;
-};
+// (staging: the pinned block holds what is copied either way; the device block, at the same offsets, also the masks nobody asked
+// for: the feature lookup reads them)
+struct dsdtm_motion_ctx : dsdtm::AddonCtx {};
 
 struct dsdtm_motion_model {
     dsdtm_motion_ctx* ctx = nullptr;
@@ -37,91 +30,9 @@ struct dsdtm_motion_model {
     float* generation(int g) const { return d_state + (size_t)g * MOTION_ARRAYS * cells; }
 };
 
-static thread_local char g_create_err[512] = "";
-
-static void set_err(dsdtm_motion_ctx* ctx, const char* fmt, ...) {
-    char* dst = ctx ? ctx->err : g_create_err;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(dst, 512, fmt, ap);
-    va_end(ap);
-}
-
-#define HIP_TRY(ctx, call)                                                                   \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return DSDTM_ERR_HIP;                                                            \
-        }                                                                                    \
-    } while (0)
-// HIP_TRY behind the first enqueue: answered by the enclosing `fail` lambda (which waits for what was enqueued)
-#define API_TRY(call)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
-    } while (0)
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-extern "C" const char* dsdtm_motion_last_error(const dsdtm_motion_ctx* ctx) { return ctx ? ctx->err : g_create_err; }
-
-extern "C" int dsdtm_motion_create(int device, dsdtm_motion_ctx** out) {
-    if (!out) return DSDTM_ERR_INVALID;
-    *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-        set_err(nullptr, "no HIP device visible (%s); dsdtm_amd_motion has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-        return DSDTM_ERR_NO_DEVICE;
-    }
-    if (device < 0 || device >= n) { set_err(nullptr, "device %d out of range (%d visible)", device, n); return DSDTM_ERR_NO_DEVICE; }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { set_err(nullptr, "hipGetDeviceProperties(%d) failed", device); return DSDTM_ERR_NO_DEVICE; }
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_err(nullptr, "device %d is %s; this library contains gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return DSDTM_ERR_NO_DEVICE;
-    }
-    dsdtm_motion_ctx* ctx = new (std::nothrow) dsdtm_motion_ctx();
-    if (!ctx) return DSDTM_ERR_NOMEM;
-    ctx->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_err(nullptr, "hipSetDevice/hipStreamCreate failed on device %d", device);
-        delete ctx;
-        return DSDTM_ERR_HIP;
-    }
-    *out = ctx;
-    return DSDTM_OK;
-}
-
-extern "C" void dsdtm_motion_destroy(dsdtm_motion_ctx* ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); (void)hipStreamDestroy(ctx->stream); }
-    if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-    delete ctx;
-}
-
-// the pinned block holds what is copied either way; the device block also the masks nobody asked for (the feature lookup reads them)
-static int ensure_stage(dsdtm_motion_ctx* ctx, size_t h_bytes, size_t d_bytes) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (h_bytes > ctx->h_cap) {
-        if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-        ctx->h_pinned = nullptr; ctx->h_cap = 0;
-        const size_t cap = align_up(h_bytes + h_bytes / 4, 1 << 16);
-        HIP_TRY(ctx, hipHostMalloc(&ctx->h_pinned, cap, hipHostMallocDefault));
-        ctx->h_cap = cap;
-    }
-    if (d_bytes > ctx->d_cap) {
-        if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-        ctx->d_stage = nullptr; ctx->d_cap = 0;
-        const size_t cap = align_up(d_bytes + d_bytes / 4, 1 << 16);
-        HIP_TRY(ctx, hipMalloc(&ctx->d_stage, cap));
-        ctx->d_cap = cap;
-    }
-    return DSDTM_OK;
-}
+extern "C" const char* dsdtm_motion_last_error(const dsdtm_motion_ctx* ctx) { return addon_last_error(ctx); }
+extern "C" int dsdtm_motion_create(int device, dsdtm_motion_ctx** out) { return addon_create("dsdtm_amd_motion", device, out); }
+extern "C" void dsdtm_motion_destroy(dsdtm_motion_ctx* ctx) { addon_destroy(ctx); }
 
 // Where an image of the caller lives (0: host memory, ordinary or pinned; 2: this device's memory; -1: another device's)
 static int image_memory(dsdtm_motion_ctx* ctx, const void* p) {

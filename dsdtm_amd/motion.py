@@ -6,9 +6,10 @@ No fallback: loading raises if the library has not been built, a context raises 
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
+
+from . import _addon
 
 LIB_NAME = "libdsdtm_amd_motion.so"
 # every symbol include/dsdtm_amd_motion.h declares
@@ -33,64 +34,27 @@ class MotionError(RuntimeError):
         self.status, self.message = status, message
 
 
-_LIB = None
-
-
 def lib_path() -> str:
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
+    return _addon.lib_path(LIB_NAME)
+
+
+def _not_built(path):
+    return FileNotFoundError(f"{path} has not been built (python dsdtm_amd/csrc/build.py --all); there is no fallback")
 
 
 def load():
     """Load libdsdtm_amd_motion.so. Raises if it has not been built (dsdtm_amd/csrc/build.py --all)."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    path = lib_path()
-    if not os.path.exists(path):
-        raise FileNotFoundError(f"{path} has not been built (python dsdtm_amd/csrc/build.py --all); there is no fallback")
-    lib = C.CDLL(path)
     vp, i = C.c_void_p, C.c_int
-    sigs = {"dsdtm_motion_create": (i, [i, C.POINTER(vp)]), "dsdtm_motion_destroy": (None, [vp]),
-            "dsdtm_motion_last_error": (C.c_char_p, [vp]), "dsdtm_motion_model_create": (i, [vp, i, i, C.POINTER(vp)]),
-            "dsdtm_motion_model_destroy": (None, [vp, vp]), "dsdtm_motion_model_reset": (i, [vp, vp]),
-            "dsdtm_motion_model_read": (i, [vp, vp, vp]), "dsdtm_motion_model_write": (i, [vp, vp, vp]),
-            "dsdtm_motion_step": (i, [vp, vp, vp, i, vp, vp, i, i, vp, vp]), "dsdtm_motion_steps": (i, [vp, i, C.POINTER(Desc)])}
-    for name, (res, args) in sigs.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    _LIB = lib
-    return lib
+    return _addon.load_addon(LIB_NAME, {
+        **_addon.context_signatures("dsdtm_motion"), "dsdtm_motion_model_create": (i, [vp, i, i, C.POINTER(vp)]),
+        "dsdtm_motion_model_destroy": (None, [vp, vp]), "dsdtm_motion_model_reset": (i, [vp, vp]),
+        "dsdtm_motion_model_read": (i, [vp, vp, vp]), "dsdtm_motion_model_write": (i, [vp, vp, vp]),
+        "dsdtm_motion_step": (i, [vp, vp, vp, i, vp, vp, i, i, vp, vp]), "dsdtm_motion_steps": (i, [vp, i, C.POINTER(Desc)])}, _not_built)
 
 
-class MotionContext:
+class MotionContext(_addon.AddonContext):
     """A dsdtm_motion_ctx: its own stream and staging block on one device. One per calling thread."""
-
-    def __init__(self, device: int = 0):
-        self.lib = load()
-        self.device = device
-        h = C.c_void_p()
-        st = self.lib.dsdtm_motion_create(device, C.byref(h))
-        if st != OK:
-            raise MotionError(st, (self.lib.dsdtm_motion_last_error(None) or b"").decode())
-        self.handle = h
-
-    def last_error(self) -> str:
-        return (self.lib.dsdtm_motion_last_error(self.handle) or b"").decode()
-
-    def check(self, st):
-        if st != OK:
-            raise MotionError(st, self.last_error())
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.dsdtm_motion_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, ERROR, load = "dsdtm_motion", MotionError, staticmethod(load)
 
     def prepare(self, steps) -> "PreparedSteps":
         """A dsdtm_motion_steps call built once (descriptors, output arrays), to be run any number of times."""

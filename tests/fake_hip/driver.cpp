@@ -14,16 +14,12 @@
 #include <vector>
 
 #include "../../include/dsdtm_amd.h"
+#include "driver_check.h"
 #include "fake_hip.h"
 
 extern "C" long long dsdtm_debug_recovered_launches(dsdtm_ctx*);
 extern "C" long long dsdtm_debug_team_seq(dsdtm_ctx*, long long);
 extern "C" int dsdtm_debug_set_option(const char*, int);
-
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return false; } \
-    } while (0)
 
 static const int W = 64, H = 48, L = 3;
 struct Geometry { int w[8], h[8], st[8]; size_t off[8]; size_t pitch; };

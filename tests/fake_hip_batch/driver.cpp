@@ -10,12 +10,8 @@
 #include <vector>
 
 #include "../../include/dsdtm_amd.h"
+#include "driver_check.h"
 #include "fake_hip.h"
-
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return false; } \
-    } while (0)
 
 static const int W = 64, H = 48, L = 3, NF = 5;
 

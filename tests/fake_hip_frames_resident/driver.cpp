@@ -12,13 +12,9 @@
 #include <vector>
 
 #include "../../include/dsdtm_amd.h"
+#include "driver_check.h"
 #include "fake_hip.h"
 #include "fake_rgbd.h"
-
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return false; } \
-    } while (0)
 
 static const int W = 64, H = 48, L = 3, NF = 7;
 static const dsdtm_camera CAM = {60.f, 60.f, 32.f, 24.f, 60.f, W, H};

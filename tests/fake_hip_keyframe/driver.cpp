@@ -11,13 +11,10 @@
 #include <vector>
 
 #include "../../include/dsdtm_amd_keyframe.h"
+#include "addon_create_failures.h"
+#include "driver_check.h"
 #include "fake_hip.h"
 #include "fake_keyframe.h"
-
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return false; } \
-    } while (0)
 
 static const dsdtm_camera CAM{512.f, 512.f, 320.f, 240.f, 512.f, 640, 480};
 static dsdtm_keyframe_params params() { dsdtm_keyframe_params p{}; p.min_valid = 30; p.max_valid = 50; p.px_samples = 31; p.min_px_median = 40; p.min_rot = p.min_trans = 0.08; return p; }
@@ -63,12 +60,8 @@ struct Batch {
         prefill();
     }
     void refresh() { d.clear(); for (auto& x : t) d.push_back(x.d); }
-    void prefill() { memset(v.data(), 0xA5, v.size() * sizeof(dsdtm_keyframe_verdict)); }
-    bool untouched() const {
-        const uint8_t* b = (const uint8_t*)v.data();
-        for (size_t i = 0; i < v.size() * sizeof(dsdtm_keyframe_verdict); ++i) if (b[i] != 0xA5) return false;
-        return true;
-    }
+    void prefill() { fill_a5(v.data(), v.size() * sizeof(dsdtm_keyframe_verdict)); }
+    bool untouched() const { return all_a5(v.data(), v.size() * sizeof(dsdtm_keyframe_verdict)); }
     int run(dsdtm_keyframe_ctx* ctx, const dsdtm_keyframe_params& p) { return dsdtm_need_keyframes(ctx, &CAM, &p, (int)d.size(), d.data(), v.data()); }
     bool answered() const { for (size_t i = 0; i < t.size(); ++i) if (!t[i].answered(v[i])) return false; return true; }
 };
@@ -208,9 +201,13 @@ static bool rejected_in_the_middle() {
     return true;
 }
 
+static bool create_failures() {
+    return addon_create_failures("dsdtm_amd_keyframe", dsdtm_keyframe_create, dsdtm_keyframe_destroy, dsdtm_keyframe_last_error);
+}
+
 int main(int argc, char** argv) {
     const std::pair<std::string, bool (*)()> all[] = {{"keyframe_failures", keyframe_failures}, {"keyframe_limits", keyframe_limits},
-                                                      {"rejected_in_the_middle", rejected_in_the_middle}};
+                                                      {"rejected_in_the_middle", rejected_in_the_middle}, {"create_failures", create_failures}};
     int failed = 0;
     for (const auto& sc : all) {
         bool wanted = argc < 2;

@@ -10,13 +10,10 @@
 #include <vector>
 
 #include "../../include/dsdtm_amd_motion.h"
+#include "addon_create_failures.h"
+#include "driver_check.h"
 #include "fake_hip.h"
 #include "fake_motion.h"
-
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return false; } \
-    } while (0)
 
 static const double IDENT[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 
@@ -49,12 +46,8 @@ struct Step {
         prefill();
         return true;
     }
-    void prefill() { std::fill(mask.begin(), mask.end(), 0xA5); std::fill(flags.begin(), flags.end(), 0xA5); }
-    bool untouched() const {
-        for (uint8_t b : mask) if (b != 0xA5) return false;
-        for (uint8_t b : flags) if (b != 0xA5) return false;
-        return true;
-    }
+    void prefill() { fill_a5(mask.data(), mask.size()); fill_a5(flags.data(), flags.size()); }
+    bool untouched() const { return all_a5(mask.data(), mask.size()) && all_a5(flags.data(), flags.size()); }
     uint8_t on(int x, int y) const { return img[(size_t)y * stride + x] >= 128 ? 255 : 0; }
     bool answered() const {          // what the fake launches leave (fake_motion.cpp)
         if (!mask.empty())
@@ -311,9 +304,14 @@ static bool argument_checks() {
     return true;
 }
 
+static bool create_failures() {
+    return addon_create_failures("dsdtm_amd_motion", dsdtm_motion_create, dsdtm_motion_destroy, dsdtm_motion_last_error);
+}
+
 int main(int argc, char** argv) {
     const std::pair<std::string, bool (*)()> all[] = {{"step_failures", step_failures}, {"model_failures", model_failures},
-                                                      {"batch_rules", batch_rules}, {"argument_checks", argument_checks}};
+                                                      {"batch_rules", batch_rules}, {"argument_checks", argument_checks},
+                                                      {"create_failures", create_failures}};
     int failed = 0;
     for (const auto& sc : all) {
         bool wanted = argc < 2;

@@ -11,9 +11,10 @@ these scenarios when its fix is reverted (shown when the job was added: a_no_for
 sharded_error_midway; re-run on the context's stream -> recover_slots_past_64; no sticky flag -> evicted_timeout_is_reported;
 no second download -> sharded_refetches_after_rerun; no re-zeroing at the epoch wrap -> team_epoch_wrap_hazard_is_real)."""
 import os
-import subprocess
 
 import pytest
+
+from tests import fake_hip_build as fhb
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fake_hip")
 SCENARIOS = ["ring_table_past_16_streams", "evicted_timeout_is_reported", "recover_slots_past_64", "team_epoch_wrap_is_cleared",
@@ -23,27 +24,17 @@ SCENARIOS = ["ring_table_past_16_streams", "evicted_timeout_is_reported", "recov
 
 
 @pytest.fixture(scope="module")
-def drivers():
-    subprocess.run(["make", "-s", "-C", HERE, "all"], check=True)
-    return os.path.join(HERE, "_build", "driver_asan"), os.path.join(HERE, "_build", "driver_tsan")
-
-
-def _run(exe, env, scenarios=()):
-    r = subprocess.run([exe, *scenarios], capture_output=True, text=True, timeout=900, env=dict(os.environ, **env))
-    lines = [l for l in r.stdout.splitlines() if l.startswith(("ok ", "FAILED "))]
-    return r, lines
+def drivers(tmp_path_factory):
+    out = tmp_path_factory.mktemp("fake_hip")
+    return [fhb.build_driver(out, san, [os.path.join(HERE, "driver.cpp")], "api.cpp", defines=["DSDTM_DIAG=1"]) for san in ("asan", "tsan")]
 
 
 def test_host_bookkeeping_under_address_and_ub_sanitizers(drivers):
-    r, lines = _run(drivers[0], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    r, lines = fhb.run_driver(drivers[0], "asan")
     assert lines == ["ok " + s for s in SCENARIOS], lines
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr
 
 
 def test_two_contexts_on_two_threads_under_thread_sanitizer(drivers):
-    r, lines = _run(drivers[1], {"TSAN_OPTIONS": "halt_on_error=1"},
-                    ["two_contexts_two_threads", "ring_table_past_16_streams", "recover_slots_past_64", "sharded_refetches_after_rerun", "streamed_entry"])
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    r, lines = fhb.run_driver(drivers[1], "tsan",
+                              ["two_contexts_two_threads", "ring_table_past_16_streams", "recover_slots_past_64", "sharded_refetches_after_rerun", "streamed_entry"])
     assert len(lines) == 5 and all(l.startswith("ok ") for l in lines), lines
-    assert "ThreadSanitizer" not in r.stderr

@@ -11,10 +11,10 @@ import subprocess
 import numpy as np
 
 from dsdtm_amd import capi, tum
+from tests import fake_hip_build as fhb
 from tests import rgbd_restatement as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = os.path.join(ROOT, "tests", "fake_hip")
 HERE = os.path.join(ROOT, "tests", "fake_hip_prefetch")
 NEW = ["dsdtm_frame_prefetch", "dsdtm_frame_wait", "dsdtm_track_frame_on", "dsdtm_frame_lift"]
 
@@ -59,29 +59,15 @@ def test_lift_restatement_on_a_hand_made_case():
 
 
 def _build(tmp_path, san):
-    exe = str(tmp_path / f"driver_{san}")
-    flags = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wno-unused-function", "-pthread"]
-    flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if san == "asan" else ["-fsanitize=thread"]
-    subprocess.run([os.environ.get("CXX", "g++"), *flags, "-I", FAKE, "-I", HERE, "-I", os.path.join(ROOT, "dsdtm_amd", "csrc"),
-                    os.path.join(HERE, "driver.cpp"), os.path.join(HERE, "fake_rgbd.cpp"), os.path.join(FAKE, "fake_hip.cpp"),
-                    os.path.join(ROOT, "dsdtm_amd", "csrc", "api.cpp"), "-o", exe], check=True)
-    return exe
+    return fhb.build_driver(tmp_path, san, [os.path.join(HERE, "driver.cpp"), os.path.join(HERE, "fake_rgbd.cpp")], "api.cpp", include_dirs=[HERE])
 
 
 def test_prefetch_path_under_address_and_ub_sanitizers(tmp_path):
-    exe = _build(tmp_path, "asan")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    lines = [l for l in r.stdout.splitlines() if l.startswith(("ok ", "FAILED "))]
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    r, lines = fhb.run_driver(_build(tmp_path, "asan"), "asan")
     assert lines == ["ok prefetch_failures", "ok ring_slot_reuse", "ok pooled_pending_buffer", "ok destroy_with_a_prefetch_pending",
                      "ok prefetch_then_track", "ok two_contexts_two_threads"], lines
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr
 
 
 def test_two_contexts_prefetching_under_thread_sanitizer(tmp_path):
-    exe = _build(tmp_path, "tsan")
-    r = subprocess.run([exe, "two_contexts_two_threads"], capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert "ok two_contexts_two_threads" in r.stdout and "ThreadSanitizer" not in r.stderr
+    r, lines = fhb.run_driver(_build(tmp_path, "tsan"), "tsan", ["two_contexts_two_threads"])
+    assert "ok two_contexts_two_threads" in r.stdout

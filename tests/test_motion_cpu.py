@@ -13,6 +13,7 @@ import pytest
 
 from dsdtm_amd import capi, motion
 from dsdtm_amd import motion_restatement as R
+from tests import fake_hip_build as fhb
 from tests import motion_cases as mc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -189,16 +190,8 @@ def test_header_documents_the_scope_and_the_traps():
 
 
 def test_host_side_under_address_and_ub_sanitizers(tmp_path):
-    fake, here = os.path.join(ROOT, "tests", "fake_hip"), os.path.join(ROOT, "tests", "fake_hip_motion")
-    exe = str(tmp_path / "driver_asan")
-    flags = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wno-unused-function", "-pthread",
-             "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    subprocess.run([os.environ.get("CXX", "g++"), *flags, "-I", fake, "-I", here, "-I", os.path.join(ROOT, "dsdtm_amd", "csrc"),
-                    os.path.join(here, "driver.cpp"), os.path.join(here, "fake_motion.cpp"), os.path.join(fake, "fake_hip.cpp"),
-                    os.path.join(ROOT, "dsdtm_amd", "csrc", "motion_api.cpp"), "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    lines = [l for l in r.stdout.splitlines() if l.startswith(("ok ", "FAILED "))]
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert lines == ["ok step_failures", "ok model_failures", "ok batch_rules", "ok argument_checks"], lines
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr
+    here = os.path.join(ROOT, "tests", "fake_hip_motion")
+    exe = fhb.build_driver(tmp_path, "asan", [os.path.join(here, "driver.cpp"), os.path.join(here, "fake_motion.cpp")], "motion_api.cpp",
+                           include_dirs=[here])
+    r, lines = fhb.run_driver(exe, "asan")
+    assert lines == ["ok step_failures", "ok model_failures", "ok batch_rules", "ok argument_checks", "ok create_failures"], lines

@@ -9,9 +9,9 @@ import subprocess
 import pytest
 
 from dsdtm_amd import capi
+from tests import fake_hip_build as fhb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = os.path.join(ROOT, "tests", "fake_hip")
 DRIVER = os.path.join(ROOT, "tests", "fake_hip_batch", "driver.cpp")
 
 
@@ -32,27 +32,14 @@ def test_release_library_exports_the_entry_and_reads_no_environment():
 
 
 def _build(tmp_path, san):
-    exe = str(tmp_path / f"driver_{san}")
-    flags = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-DDSDTM_DIAG=1", "-Wall", "-Wno-unused-function", "-pthread"]
-    flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if san == "asan" else ["-fsanitize=thread"]
-    subprocess.run([os.environ.get("CXX", "g++"), *flags, "-I", FAKE, "-I", os.path.join(ROOT, "dsdtm_amd", "csrc"), DRIVER,
-                    os.path.join(FAKE, "fake_hip.cpp"), os.path.join(ROOT, "dsdtm_amd", "csrc", "api.cpp"), "-o", exe], check=True)
-    return exe
+    return fhb.build_driver(tmp_path, san, [DRIVER], "api.cpp", defines=["DSDTM_DIAG=1"])
 
 
 def test_batch_entry_under_address_and_ub_sanitizers(tmp_path):
-    exe = _build(tmp_path, "asan")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    lines = [l for l in r.stdout.splitlines() if l.startswith(("ok ", "FAILED "))]
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    r, lines = fhb.run_driver(_build(tmp_path, "asan"), "asan")
     assert lines == ["ok batch_failures", "ok batch_image_arrivals", "ok two_contexts_two_threads"], lines
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr
 
 
 def test_two_contexts_running_batches_under_thread_sanitizer(tmp_path):
-    exe = _build(tmp_path, "tsan")
-    r = subprocess.run([exe, "two_contexts_two_threads"], capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert "ok two_contexts_two_threads" in r.stdout and "ThreadSanitizer" not in r.stderr
+    r, lines = fhb.run_driver(_build(tmp_path, "tsan"), "tsan", ["two_contexts_two_threads"])
+    assert "ok two_contexts_two_threads" in r.stdout
