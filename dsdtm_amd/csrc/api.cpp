@@ -1,4 +1,4 @@
-// api.cpp — the C ABI of include/dsdtm_amd.h: context, host staging, launches.
+// api.cpp — the C ABI of include/dsdtm_amd.h: context, host staging, launches (local BA: api_local_ba.cpp; shared: api_internal.h).
 //
 // Host entry points pack their inputs into one pinned buffer, move it with a single
 // hipMemcpyAsync, launch on the context's stream and copy the (small) results back. Device
@@ -17,112 +17,10 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/dsdtm_amd.h"
-#include "kernels.h"
+#include "api_internal.h"
 
 using namespace dsdtm;
-
-struct dsdtm_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    char err[512] = {0};
-    // staging
-    void* h_pinned = nullptr;
-    size_t h_cap = 0;
-    void* d_stage = nullptr;
-    size_t d_cap = 0;
-    // workspace for the generic sparse-align kernel
-    void* d_ws = nullptr;
-    size_t ws_cap = 0;
-    // Pair counters of the persistent sparse-align kernel (a launch's slots pull pair indices from one word; the
-    // word is zero when a launch starts and the launch's last claim puts it back to zero). A word must never be
-    // shared by two launches that can run at the same time, so:
-    //  * every stream that launches through this context owns a ring of COUNTERS_PER_STREAM words (a stream runs
-    //    its launches in order, so the previous user of a word has finished when the next one starts);
-    //  * a launch captured into a hipGraph gets a word of its own from the graph pool, for the life of the
-    //    context, and a memset node in front of it (a hipGraphExec never overlaps itself).
-    unsigned* d_counter = nullptr;
-    // + the stream's workspace, and an event recorded behind the entry's last launch: what a 17th stream waits for
-    // before it takes the entry over (the old stream itself may be gone by then)
-    struct StreamRing { hipStream_t stream; unsigned seq; bool used; void* d_ws; size_t ws_cap; unsigned long long last_use; hipEvent_t last; bool last_recorded; };
-    unsigned long long ring_tick = 0;
-    static constexpr int MAX_STREAMS = 16, COUNTERS_PER_STREAM = 8, GRAPH_COUNTERS = 256;
-    StreamRing rings[MAX_STREAMS] = {};
-    int graph_counters_used = 0;
-    // Exchange buffers of the team kernel: a ring of 8 launches x 64 pairs. Team launches of one context are
-    // totally ordered (a launch on another stream first waits for the previous team launch's event), because the
-    // members of a team spin on each other and must all be resident at once.
-    uint8_t* d_team = nullptr;
-    unsigned team_seq = 0;
-    unsigned long long team_wraps = 0;    // times the 20-bit launch epoch of the exchange tags wrapped (ring re-zeroed each time)
-    hipEvent_t team_event = nullptr;      // recorded behind the last team launch that ran on a caller's stream
-    hipStream_t team_last_stream = nullptr;
-    bool team_any = false;
-    // Hand-over timeout words: host-mapped pinned memory of THIS context (a wave whose bounded wait ran out stores 1;
-    // the host reads the word once the launch's stream has drained — no copy, no device-global state):
-    //   [0, MAX_STREAMS)            one per stream ring: the one-CU launches of that stream
-    //   FLAG_GRAPH                  launches captured into hipGraphs
-    //   FLAG_SINGLE                 the synchronous single-pair entry points
-    //   FLAG_RECOVER + slot         one per multi-CU launch (team / two-member kernels) that has not been settled yet
-    static constexpr int RECOVER_SLOTS = 64;
-    static constexpr int FLAG_GRAPH = MAX_STREAMS, FLAG_SINGLE = MAX_STREAMS + 1, FLAG_RECOVER = MAX_STREAMS + 2,
-                         N_FLAGS = FLAG_RECOVER + RECOVER_SLOTS;
-    volatile unsigned* h_flags = nullptr;
-    unsigned* d_flags = nullptr;
-    // Multi-CU launches wait on partner workgroups, i.e. on the GPU's dispatch: a wait that runs out (a foreign load on
-    // the device, another partition mode) must not fail the caller. Every such launch leaves what a re-run needs —
-    // descriptor, a copy of its seed poses, an event — and is settled by dsdtm_sparse_align_check (or when its slot is
-    // needed again): timeout word clear -> forgotten; set -> poses re-seeded, the same batch relaunched on the one-CU
-    // kernels, which cannot wait for anything outside their own workgroup.
-    struct Recover {
-        bool used = false;
-        dsdtm_batch_desc b; dsdtm_camera cam; dsdtm_align_params prm;
-        hipStream_t stream = nullptr;
-        hipEvent_t done = nullptr;
-        void* d_seed = nullptr; size_t seed_cap = 0;
-        unsigned long long order = 0;
-    };
-    Recover rec[RECOVER_SLOTS];
-    unsigned long long rec_tick = 0;
-    unsigned long long recovered = 0;     // launches re-run on the one-CU kernels so far (dsdtm_debug_recovered_launches)
-    bool evicted_timeout = false;         // a stream ring was handed to another stream while its timeout word was set
-    bool multi_cu_ok = true;              // the dispatch assumptions of the multi-CU kernels hold on this device
-    // dsdtm_sparse_align_batch_streamed: two copy streams and one event per chunk, created on first use
-    hipStream_t copy_stream[2] = {nullptr, nullptr};
-    std::vector<hipEvent_t> copy_events;
-    hipEvent_t copy_fence = nullptr;
-    int num_cus = 256;
-    // Pyramid buffers of destroyed frames, kept for the next frame of the same size: a live tracker creates and destroys one
-    // frame per image, and hipMalloc / hipFree (which waits for the whole device) cost more than the pyramid kernel.
-    // dsdtm_local_ba*: the descriptors (pinned + device) and the workspace of the local-BA launches, and an event behind the
-    // last one (the next launch of this context waits for it before it reuses them)
-    void* d_lba = nullptr; size_t lba_cap = 0;
-    void* h_lba = nullptr; size_t h_lba_cap = 0;
-    hipEvent_t lba_event = nullptr; bool lba_recorded = false;
-    hipEvent_t track_event = nullptr;     // dsdtm_track_frame: the local map has arrived (copied up on copy_stream[0] beside Run)
-    // dsdtm_frame_prefetch: a stream of its own, created on first use. Prefetched frames are numbered in the order they were
-    // enqueued on it; the stream runs in order, so "frame n is resident" implies every earlier one is. Event n % PREFETCH_EVENTS
-    // is recorded behind frame n (a wait on an event that a later frame has re-recorded waits a little longer, never too
-    // short). The ring is as long as two full batches of dsdtm_track_frames: with step k + 1 of 1024 trackers prefetched before
-    // step k is tracked, the event behind step k's last frame is still its own, and the call does not wait for step k + 1.
-    // An event is created when its place in the ring is first used. prefetch_settled: the highest number the HOST knows to be resident — frames up to it cost nothing more;
-    // prefetch_waiting: the highest number the context's stream has been told to wait for (hipStreamWaitEvent) — it becomes
-    // prefetch_settled at the next host synchronisation of that stream.
-    static constexpr int PREFETCH_EVENTS = 4096;
-    hipStream_t prefetch_stream = nullptr;
-    hipEvent_t prefetch_event[PREFETCH_EVENTS] = {};
-    unsigned long long prefetch_seq = 0, prefetch_settled = 0, prefetch_waiting = 0;
-    // its own pinned staging ring (the context's staging block is busy with frame k while frame k + 1 is staged): a slot
-    // is written again only after the frame that used it last is resident
-    struct PrefetchSlot { void* h; size_t cap; unsigned long long seq; };
-    PrefetchSlot prefetch_slot[2] = {};
-    unsigned prefetch_next_slot = 0;
-    // (seq: the prefetch number of the destroyed frame — a buffer may go to the pool while its frame is still pending, and
-    // its next user's stream then waits for that frame's event, see frame_alloc)
-    struct PooledFrame { size_t pitch; uint8_t* d; unsigned long long seq; };
-    static constexpr size_t FRAME_POOL = 8;
-    std::vector<PooledFrame> frame_pool;
-};
+using namespace dsdtm::detail;
 
 // Contexts that are alive (dsdtm_frame_destroy may be handed a context that is already gone: it must not be dereferenced)
 static std::mutex g_live_mutex;
@@ -134,24 +32,13 @@ static bool ctx_is_live_locked(dsdtm_ctx* ctx) {      // (g_live_mutex held)
 
 static thread_local char g_create_err[512] = "";
 
-static void set_err(dsdtm_ctx* ctx, const char* fmt, ...) {
+void dsdtm::detail::set_err(dsdtm_ctx* ctx, const char* fmt, ...) {
     char* dst = ctx ? ctx->err : g_create_err;
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(dst, 512, fmt, ap);
     va_end(ap);
 }
-
-#define HIP_TRY(ctx, call)                                                                   \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return DSDTM_ERR_HIP;                                                            \
-        }                                                                                    \
-    } while (0)
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // A pyramid as it lies on the device: dense rows, every level at a 64-byte aligned offset
 struct PackedPyr {
@@ -401,7 +288,7 @@ void dsdtm_destroy(dsdtm_ctx* ctx) {
 
 }  // extern "C"
 
-static int ensure_stage(dsdtm_ctx* ctx, size_t bytes) {
+int dsdtm::detail::ensure_stage(dsdtm_ctx* ctx, size_t bytes) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (bytes > ctx->h_cap) {
         if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -1395,8 +1282,8 @@ extern "C" void dsdtm_frame_destroy(dsdtm_ctx* ctx, dsdtm_frame* f) {
 }
 
 // ---- RGB-D frames that enter the device ahead of time --------------------------------------------------------------
-// rgbd.hip defines these; weak here, as the local-BA launches below, so that a host-only build of this file without the
-// kernels still links. The entry points test them and fail cleanly where they are missing.
+// rgbd.hip defines these; weak here so that a host-only build of this file without the kernels (the fake-HIP sanitizer
+// drivers under tests/ that do not fake them) still links. The entry points test them and fail cleanly where they are missing.
 namespace dsdtm {
 __attribute__((weak)) hipError_t depth_ingest_launch(const uint16_t* src, int src_stride, float* dst, int w, int h, float inv_scale,
                                                      int num_cus, hipStream_t stream);
@@ -2172,186 +2059,6 @@ extern "C" int dsdtm_pose_optimization(dsdtm_ctx* ctx, const double* bearing, co
     memcpy(T_cur_w, h + o_T, 96);
     memcpy(summary, h + o_sm, sizeof(*summary));
     if (summary->n_residual_blocks > 0) memcpy(residual_norm, h + o_rn, (size_t)summary->n_residual_blocks * 8);
-    return DSDTM_OK;
-}
-
-// ---- Optimizer::LocalBundleAdjustment ----------------------------------------------------------------------------------
-// local_ba.hip defines these; weak here so that a host-only build of this file without the kernels (the fake-HIP
-// sanitizer drivers under tests/) still links. The entry points test them and fail cleanly where they are missing.
-namespace dsdtm {
-__attribute__((weak)) size_t local_ba_workspace_bytes(int n_pts, int n_obs);
-__attribute__((weak)) hipError_t local_ba_check_launch(const LocalBaArgs& args, hipStream_t stream);
-__attribute__((weak)) hipError_t local_ba_launch(const LocalBaArgs& args, hipStream_t stream);
-}
-static bool lba_kernels_linked() { return local_ba_workspace_bytes && local_ba_check_launch && local_ba_launch; }
-static const char* lba_check_reason(int mask) {
-    if (mask & LBA_CHECK_KF_INDEX) return "keyframe index out of range";
-    if (mask & LBA_CHECK_POINT_INDEX) return "point index out of range";
-    if (mask & LBA_CHECK_LEVEL) return "level out of range";
-    if (mask & LBA_CHECK_ORDER) return "point index decreases";
-    if (mask & LBA_CHECK_DUPLICATE) return "a keyframe observes a point twice";
-    if (mask & LBA_CHECK_NO_FREE) return "no free keyframe";
-    if (mask & LBA_CHECK_FREE_LIMIT) return "free keyframes over the limit of 16";
-    return "constant keyframes over the limit of 64";
-}
-static int lba_check_counts(dsdtm_ctx* ctx, int i, const dsdtm_local_ba_problem& q) {
-    const char* what = nullptr;
-    // (the release library holds no DSDTM_* string: the limits are named by their values)
-    int limit = 0;
-    if (q.n_keyframes <= 0) what = "no keyframe (at least one free keyframe is needed)";
-    else if (q.n_keyframes > DSDTM_LBA_MAX_FREE_KF + DSDTM_LBA_MAX_CONST_KF)
-        what = "keyframes over the limit of free + constant keyframes", limit = DSDTM_LBA_MAX_FREE_KF + DSDTM_LBA_MAX_CONST_KF;
-    else if (q.n_points < 0 || q.n_points > DSDTM_LBA_MAX_POINTS) what = "points outside 0 .. the point limit", limit = DSDTM_LBA_MAX_POINTS;
-    else if (q.n_observations < 0 || q.n_observations > DSDTM_LBA_MAX_OBSERVATIONS)
-        what = "observations outside 0 .. the observation limit", limit = DSDTM_LBA_MAX_OBSERVATIONS;
-    else if (q.keyframe_offset < 0 || q.point_offset < 0 || q.observation_offset < 0) what = "negative offset";
-    if (!what) return DSDTM_OK;
-    set_err(ctx, "local_ba: problem %d: %s (%d)", i, what, limit);
-    return DSDTM_ERR_INVALID;
-}
-
-extern "C" int dsdtm_local_ba_batch_device(dsdtm_ctx* ctx, int n_problems, const dsdtm_local_ba_problem* problems,
-                                           double* T_c2w, const uint8_t* kf_constant, double* points,
-                                           const int32_t* obs_kf, const int32_t* obs_point, const double* obs_bearing,
-                                           const int32_t* obs_level, const dsdtm_local_ba_params* params,
-                                           uint8_t* outlier, dsdtm_local_ba_summary* summary, void* hip_stream) {
-    if (!ctx) return DSDTM_ERR_INVALID;
-    if (n_problems < 0 || !params || params->max_iterations < 0 || !(params->delta >= 0.0) || !std::isfinite(params->delta)) {
-        set_err(ctx, "local_ba: bad argument"); return DSDTM_ERR_INVALID;
-    }
-    if (n_problems == 0) return DSDTM_OK;
-    if (!problems || !T_c2w || !kf_constant || !points || !obs_kf || !obs_point || !obs_bearing || !obs_level || !outlier || !summary) {
-        set_err(ctx, "local_ba: NULL argument"); return DSDTM_ERR_INVALID;
-    }
-    if (!lba_kernels_linked()) { set_err(ctx, "local_ba: this build has no local-BA kernels"); return DSDTM_ERR_NO_DEVICE; }
-    // every problem is checked before the solve is enqueued: one bad problem and no problem runs, nothing is written
-    std::vector<LocalBaProblemDev> dev((size_t)n_problems);
-    size_t ws = 0;
-    for (int i = 0; i < n_problems; ++i) {
-        const dsdtm_local_ba_problem& q = problems[i];
-        if (int rc = lba_check_counts(ctx, i, q)) return rc;
-        LocalBaProblemDev& d = dev[(size_t)i];
-        d.n_kf = q.n_keyframes; d.n_pts = q.n_points; d.n_obs = q.n_observations; d.reserved = 0;
-        d.kf_off = q.keyframe_offset; d.pt_off = q.point_offset; d.obs_off = q.observation_offset;
-        d.ws_off = (int64_t)ws;
-        ws += local_ba_workspace_bytes(q.n_points, q.n_observations);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->lba_event) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->lba_event, hipEventDisableTiming));
-    if (ctx->lba_recorded) HIP_TRY(ctx, hipEventSynchronize(ctx->lba_event));    // the previous launch is done with the buffers
-    const size_t desc_bytes = align_up(dev.size() * sizeof(LocalBaProblemDev), 256);
-    const size_t check_bytes = align_up(dev.size() * sizeof(int32_t), 256);
-    const size_t dev_bytes = desc_bytes + check_bytes + ws, host_bytes = desc_bytes + check_bytes;
-    if (dev_bytes > ctx->lba_cap) {
-        if (ctx->d_lba) (void)hipFree(ctx->d_lba);
-        ctx->d_lba = nullptr; ctx->lba_cap = 0;
-        const size_t cap = align_up(dev_bytes + dev_bytes / 4, 1 << 16);
-        HIP_TRY(ctx, hipMalloc(&ctx->d_lba, cap));
-        ctx->lba_cap = cap;
-    }
-    if (host_bytes > ctx->h_lba_cap) {
-        if (ctx->h_lba) (void)hipHostFree(ctx->h_lba);
-        ctx->h_lba = nullptr; ctx->h_lba_cap = 0;
-        HIP_TRY(ctx, hipHostMalloc(&ctx->h_lba, host_bytes, hipHostMallocDefault));
-        ctx->h_lba_cap = host_bytes;
-    }
-    memcpy(ctx->h_lba, dev.data(), dev.size() * sizeof(LocalBaProblemDev));
-    const hipStream_t stream = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lba, ctx->h_lba, dev.size() * sizeof(LocalBaProblemDev), hipMemcpyHostToDevice, stream));
-    LocalBaArgs a;
-    a.n_problems = n_problems; a.max_iterations = params->max_iterations; a.delta = params->delta;
-    a.problems = (const LocalBaProblemDev*)ctx->d_lba;
-    a.T = T_c2w; a.kf_const = kf_constant; a.points = points;
-    a.obs_kf = obs_kf; a.obs_pt = obs_point; a.bearing = obs_bearing; a.level = obs_level;
-    a.outlier = outlier; a.summary = summary;
-    a.check = (int32_t*)((uint8_t*)ctx->d_lba + desc_bytes);
-    a.ws = (uint8_t*)ctx->d_lba + desc_bytes + check_bytes;
-    // the checks of the device arrays (indices, levels, order, constant flags): a read-only kernel whose masks are read back
-    // here — the call waits until the stream has reached them; the solve itself stays asynchronous
-    HIP_TRY(ctx, local_ba_check_launch(a, stream));
-    int32_t* h_check = (int32_t*)((uint8_t*)ctx->h_lba + desc_bytes);
-    HIP_TRY(ctx, hipMemcpyAsync(h_check, a.check, dev.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->lba_event, stream));
-    ctx->lba_recorded = true;
-    HIP_TRY(ctx, hipEventSynchronize(ctx->lba_event));
-    for (int i = 0; i < n_problems; ++i)
-        if (h_check[i]) { set_err(ctx, "local_ba: problem %d: %s", i, lba_check_reason(h_check[i])); return DSDTM_ERR_INVALID; }
-    HIP_TRY(ctx, local_ba_launch(a, stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->lba_event, stream));
-    ctx->lba_recorded = true;
-    return DSDTM_OK;
-}
-
-extern "C" int dsdtm_local_ba(dsdtm_ctx* ctx, int n_keyframes, double* T_c2w, const uint8_t* kf_constant,
-                              int n_points, double* points, int n_observations, const int32_t* obs_kf, const int32_t* obs_point,
-                              const double* obs_bearing, const int32_t* obs_level, const dsdtm_local_ba_params* params,
-                              uint8_t* outlier, dsdtm_local_ba_summary* summary) {
-    if (!ctx) return DSDTM_ERR_INVALID;
-    if (!params || params->max_iterations < 0 || !(params->delta >= 0.0) || !std::isfinite(params->delta)) {
-        set_err(ctx, "local_ba: bad argument"); return DSDTM_ERR_INVALID;
-    }
-    dsdtm_local_ba_problem q = {n_keyframes, n_points, n_observations, 0, 0, 0, 0};
-    if (int rc = lba_check_counts(ctx, 0, q)) return rc;
-    if (!lba_kernels_linked()) { set_err(ctx, "local_ba: this build has no local-BA kernels"); return DSDTM_ERR_NO_DEVICE; }
-    if (!T_c2w || !kf_constant || !summary || (n_points > 0 && !points) ||
-        (n_observations > 0 && (!obs_kf || !obs_point || !obs_bearing || !obs_level || !outlier))) {
-        set_err(ctx, "local_ba: NULL argument"); return DSDTM_ERR_INVALID;
-    }
-    int n_free = 0;
-    for (int k = 0; k < n_keyframes; ++k) n_free += kf_constant[k] ? 0 : 1;
-    if (n_free == 0) { set_err(ctx, "local_ba: no free keyframe"); return DSDTM_ERR_INVALID; }
-    if (n_free > DSDTM_LBA_MAX_FREE_KF) {
-        set_err(ctx, "local_ba: %d free keyframes over the limit of %d", n_free, DSDTM_LBA_MAX_FREE_KF); return DSDTM_ERR_INVALID;
-    }
-    if (n_keyframes - n_free > DSDTM_LBA_MAX_CONST_KF) {
-        set_err(ctx, "local_ba: %d constant keyframes over the limit of %d", n_keyframes - n_free, DSDTM_LBA_MAX_CONST_KF);
-        return DSDTM_ERR_INVALID;
-    }
-    for (int i = 0; i < n_observations; ++i) {
-        const int k = obs_kf[i], p = obs_point[i], l = obs_level[i];
-        if (k < 0 || k >= n_keyframes) { set_err(ctx, "local_ba: observation %d: keyframe index %d out of range", i, k); return DSDTM_ERR_INVALID; }
-        if (p < 0 || p >= n_points) { set_err(ctx, "local_ba: observation %d: point index %d out of range", i, p); return DSDTM_ERR_INVALID; }
-        if (l < 0 || l >= DSDTM_MAX_LEVELS) { set_err(ctx, "local_ba: observation %d: level %d out of range", i, l); return DSDTM_ERR_INVALID; }
-        if (i > 0 && obs_point[i - 1] > p) { set_err(ctx, "local_ba: observation %d: point index decreases", i); return DSDTM_ERR_INVALID; }
-        for (int j = i - 1; j >= 0 && obs_point[j] == p; --j)
-            if (obs_kf[j] == k) { set_err(ctx, "local_ba: observation %d: keyframe %d observes point %d twice", i, k, p); return DSDTM_ERR_INVALID; }
-    }
-    const size_t K = (size_t)n_keyframes, NP = (size_t)n_points, N = (size_t)n_observations;
-    size_t o = 0;
-    const size_t o_T = o;   o += align_up(K * 96, 256);        // in/out
-    const size_t o_X = o;   o += align_up(NP * 24, 256);       // in/out
-    const size_t o_out = o; o += align_up(N, 256);             // out
-    const size_t o_sm = o;  o += align_up(sizeof(dsdtm_local_ba_summary), 256);   // out
-    const size_t out_end = o;
-    const size_t o_c = o;   o += align_up(K, 256);
-    const size_t o_k = o;   o += align_up(N * 4, 256);
-    const size_t o_p = o;   o += align_up(N * 4, 256);
-    const size_t o_b = o;   o += align_up(N * 24, 256);
-    const size_t o_l = o;   o += align_up(N * 4, 256);
-    const size_t total = o;
-    if (int rc = ensure_stage(ctx, total)) return rc;
-    uint8_t* h = (uint8_t*)ctx->h_pinned;
-    uint8_t* d = (uint8_t*)ctx->d_stage;
-    memcpy(h + o_T, T_c2w, K * 96);
-    if (NP) memcpy(h + o_X, points, NP * 24);
-    memcpy(h + o_c, kf_constant, K);
-    if (N) {
-        memcpy(h + o_k, obs_kf, N * 4);
-        memcpy(h + o_p, obs_point, N * 4);
-        memcpy(h + o_b, obs_bearing, N * 24);
-        memcpy(h + o_l, obs_level, N * 4);
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = dsdtm_local_ba_batch_device(ctx, 1, &q, (double*)(d + o_T), d + o_c, (double*)(d + o_X),
-                                             (const int32_t*)(d + o_k), (const int32_t*)(d + o_p), (const double*)(d + o_b),
-                                             (const int32_t*)(d + o_l), params, d + o_out,
-                                             (dsdtm_local_ba_summary*)(d + o_sm), ctx->stream)) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(h, d, out_end, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(T_c2w, h + o_T, K * 96);
-    if (NP) memcpy(points, h + o_X, NP * 24);
-    if (N) memcpy(outlier, h + o_out, N);
-    memcpy(summary, h + o_sm, sizeof(*summary));
     return DSDTM_OK;
 }
 

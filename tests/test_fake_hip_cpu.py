@@ -26,7 +26,7 @@ SCENARIOS = ["ring_table_past_16_streams", "evicted_timeout_is_reported", "recov
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
     out = tmp_path_factory.mktemp("fake_hip")
-    return [fhb.build_driver(out, san, [os.path.join(HERE, "driver.cpp")], "api.cpp", defines=["DSDTM_DIAG=1"]) for san in ("asan", "tsan")]
+    return [fhb.build_driver(out, san, [os.path.join(HERE, "driver.cpp")], fhb.API_SOURCES, defines=["DSDTM_DIAG=1"]) for san in ("asan", "tsan")]
 
 
 def test_host_bookkeeping_under_address_and_ub_sanitizers(drivers):

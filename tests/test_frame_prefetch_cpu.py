@@ -59,7 +59,7 @@ def test_lift_restatement_on_a_hand_made_case():
 
 
 def _build(tmp_path, san):
-    return fhb.build_driver(tmp_path, san, [os.path.join(HERE, "driver.cpp"), os.path.join(HERE, "fake_rgbd.cpp")], "api.cpp", include_dirs=[HERE])
+    return fhb.build_driver(tmp_path, san, [os.path.join(HERE, "driver.cpp"), os.path.join(HERE, "fake_rgbd.cpp")], fhb.API_SOURCES, include_dirs=[HERE])
 
 
 def test_prefetch_path_under_address_and_ub_sanitizers(tmp_path):

@@ -191,7 +191,7 @@ def test_header_documents_the_scope_and_the_traps():
 
 def test_host_side_under_address_and_ub_sanitizers(tmp_path):
     here = os.path.join(ROOT, "tests", "fake_hip_motion")
-    exe = fhb.build_driver(tmp_path, "asan", [os.path.join(here, "driver.cpp"), os.path.join(here, "fake_motion.cpp")], "motion_api.cpp",
+    exe = fhb.build_driver(tmp_path, "asan", [os.path.join(here, "driver.cpp"), os.path.join(here, "fake_motion.cpp")], ["motion_api.cpp"],
                            include_dirs=[here])
     r, lines = fhb.run_driver(exe, "asan")
     assert lines == ["ok step_failures", "ok model_failures", "ok batch_rules", "ok argument_checks", "ok create_failures"], lines

@@ -11,7 +11,7 @@ HERE = os.path.join(fhb.ROOT, "tests", "fake_hip_keyframe")
 
 
 def test_need_keyframes_host_side_under_address_and_ub_sanitizers(tmp_path):
-    exe = fhb.build_driver(tmp_path, "asan", [os.path.join(HERE, "driver.cpp"), os.path.join(HERE, "fake_keyframe.cpp")], "keyframe_api.cpp",
+    exe = fhb.build_driver(tmp_path, "asan", [os.path.join(HERE, "driver.cpp"), os.path.join(HERE, "fake_keyframe.cpp")], ["keyframe_api.cpp"],
                            include_dirs=[HERE])
     r, lines = fhb.run_driver(exe, "asan")
     assert lines == ["ok keyframe_failures", "ok keyframe_limits", "ok rejected_in_the_middle", "ok create_failures"], lines

@@ -32,7 +32,7 @@ def test_release_library_exports_the_entry_and_reads_no_environment():
 
 
 def _build(tmp_path, san):
-    return fhb.build_driver(tmp_path, san, [DRIVER], "api.cpp", defines=["DSDTM_DIAG=1"])
+    return fhb.build_driver(tmp_path, san, [DRIVER], fhb.API_SOURCES, defines=["DSDTM_DIAG=1"])
 
 
 def test_batch_entry_under_address_and_ub_sanitizers(tmp_path):

@@ -88,7 +88,7 @@ def test_binding_fills_the_frame_handles_and_clears_the_images():
 
 
 def _build(tmp_path, san):
-    return fhb.build_driver(tmp_path, san, [DRIVER, os.path.join(RGBD, "fake_rgbd.cpp")], "api.cpp", include_dirs=[RGBD])
+    return fhb.build_driver(tmp_path, san, [DRIVER, os.path.join(RGBD, "fake_rgbd.cpp")], fhb.API_SOURCES, include_dirs=[RGBD])
 
 
 def test_resident_mode_under_address_and_ub_sanitizers(tmp_path):
