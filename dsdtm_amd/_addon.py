@@ -1,5 +1,5 @@
-"""What the ctypes bindings of the add-on libraries (capi: libdsdtm_amd_keyframe.so, motion: libdsdtm_amd_motion.so) share: the loader
-and the context. No fallback: loading raises if the library has not been built, a context raises without a gfx950 device."""
+"""What the ctypes bindings of the add-on libraries (capi: libdsdtm_amd_keyframe.so, motion: libdsdtm_amd_motion.so,
+homography: libdsdtm_amd_homography.so) share: the loader and the context. No fallback: loading raises if the library has not been built, a context raises without a gfx950 device."""
 from __future__ import annotations
 
 import ctypes as C

@@ -45,6 +45,10 @@ ADDONS = {
     # include/dsdtm_amd_motion.h: the moving-object mask of Tracking::MotionRemoval
     "motion": (["motion_api.cpp", "motion.hip"],
                ["motion.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_motion.h"), os.path.join(_INC, "dsdtm_amd.h")], OUT_MOTION),
+    # include/dsdtm_amd_homography.h: the RANSAC homography that the motion step takes as an argument, for n trackers
+    "homography": (["homography_api.cpp", "homography.hip"],
+                   ["homography.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_homography.h"), os.path.join(_INC, "dsdtm_amd.h")],
+                   os.path.join(HERE, "libdsdtm_amd_homography.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")
