@@ -28,6 +28,7 @@ struct PyrDownArgs {
     size_t soff;
     int dw, dh, dstride;
     size_t doff;
+    int tight;                              // fewer than 4 bytes between the source level's last row and the end of the pitch
 };
 
 // Each thread owns a strip of 4 output columns and walks down PD_ROWS output rows with a sliding
@@ -102,8 +103,9 @@ __device__ __forceinline__ uint32_t pd_pack(u16x2 oA, u16x2 oB) {
 // 4-byte aligned (2 * x4 - 4 is 4 mod 8 for every strip but the left one), so the LDS reads go through a type that
 // says so: the compiler may still pick ds_read_b64 where the hardware's unaligned DS access allows it, or two
 // ds_read2_b32, but never assumes an 8-byte alignment that does not hold. The 4th dword of the right-border strip
-// starts at the row end: in HBM it lies inside the pyramid (a source level is never the last level), in LDS inside
-// the band buffer's padding; it is not used.
+// starts at the row end: in HBM it lies in the row's padding, in the next row or, behind the last row, in whatever
+// follows the level inside the pitch — the launchers keep a level with fewer than 4 bytes there off this load
+// (pd_tight); in LDS it lies inside the band buffer's padding. It is not used.
 struct __attribute__((packed, aligned(4))) PdU32x2 { uint32_t x, y; };
 template <bool SRC_LDS>
 __device__ __forceinline__ uint4 pd_load16(const uint8_t* __restrict__ p) {
@@ -214,7 +216,9 @@ __global__ __launch_bounds__(256) void pyrdown_kernel(const PyrDownArgs a, int t
     const bool right = (xs + 10 >= a.sw);             // only column xs+10 == sw can be outside
     const bool fast = ((a.sstride & 3) == 0) && ((((size_t)src) & 3) == 0) && ((a.sw & 1) == 0) && a.sw >= 16 && a.sh >= 4 &&
                       (x4 + 3 < a.dw) && (!right || xs + 10 == a.sw) && (((size_t)(dst + x4)) & 3) == 0 && (a.dstride & 3) == 0;
-    if (fast) {
+    // a tight level (pd_tight): the right strip's tasks that reach the last source row go byte-wise
+    const bool behind = a.tight && right && 2 * y0 + 2 * PD_ROWS >= a.sh - 1;     // 2 y0 + 2 PD_ROWS: the task's last source row
+    if (fast && !behind) {
         pd_task<false, false, PD_ROWS>(src, a.sstride, 0, a.sw, a.sh, y0, x4, 0, a.dh, 2 * a.dh, nullptr, 0, dst, a.dstride, 0, a.dh);
         return;
     }
@@ -318,6 +322,14 @@ __global__ __launch_bounds__(NT) void pyrdown_fused_kernel(const PyrFusedArgs a)
                           nullptr, 0, base + a.off[K], a.stride[K], olo[K], ohi[K]);
 }
 
+// The right-border strip of the aligned fast path loads the 4 bytes behind its row (pd_load16), behind the last row of a
+// source level the 4 bytes behind the level. Does the caller's layout leave fewer than that inside the pitch? (Only a
+// row without padding reaches that far: a width that is a multiple of 8 with stride == width. The entry has checked
+// off + stride * h <= pitch.) In the last image of a batch those bytes would lie behind the caller's buffer.
+static bool pd_tight(size_t pyr_pitch, int w, int h, int stride, size_t off) {
+    return stride < w + 4 && pyr_pitch - (off + (size_t)stride * h) < 4;
+}
+
 // Can the whole pyramid go through the fused kernel? (every source level on the aligned fast path of the strip code)
 static bool pyrdown_fused_ok(const uint8_t* pyr, size_t pyr_pitch, int levels, const int* w, const int* h, const int* stride,
                              const size_t* off) {
@@ -336,6 +348,7 @@ hipError_t pyrdown_fused_launch(uint8_t* pyr, size_t pyr_pitch, int n_images, in
     *launched = false;
     if (n_images <= 0) { *launched = true; return hipSuccess; }
     if (!pyrdown_fused_ok(pyr, pyr_pitch, levels, w, h, stride, off)) return hipSuccess;
+    if (pd_tight(pyr_pitch, w[0], h[0], stride[0], off[0])) return hipSuccess;      // level 0 is the one level read from HBM
     const int K = levels - 1;
     PyrFusedArgs a;
     a.pyr = pyr; a.pyr_pitch = pyr_pitch;
@@ -427,6 +440,7 @@ hipError_t pyrdown_launch(uint8_t* pyr, size_t pyr_pitch, int n_images, int sw, 
     a.pyr = pyr; a.pyr_pitch = pyr_pitch; a.n_images = n_images;
     a.sw = sw; a.sh = sh; a.sstride = sstride; a.soff = soff;
     a.dw = (sw + 1) / 2; a.dh = (sh + 1) / 2; a.dstride = dstride; a.doff = doff;
+    a.tight = pd_tight(pyr_pitch, sw, sh, sstride, soff);
     const int ty = (a.dh + PD_ROWS - 1) / PD_ROWS;          // row chunks of PD_ROWS output rows per thread
     const int tx = (a.dw + 3) / 4;                          // strips of 4 output columns
     // gridDim.z is limited to 65535 images per launch

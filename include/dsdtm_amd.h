@@ -643,6 +643,17 @@ int dsdtm_align2d_batch_device(dsdtm_ctx* ctx, const dsdtm_image_desc* cur,
  * output size ((w+1)/2, (h+1)/2). Up to 32 images whose levels have widths that are multiples
  * of 8 (3..5 levels) are built by ONE launch (intermediate levels in LDS, a new frame of the
  * live tracker); larger batches and other shapes by one launch per level. Same bytes either way.
+ *
+ * The layout is the caller's: any stride[l] >= width[l], any level_offset[l] and any order of the
+ * levels inside pyr_pitch, as long as level_offset[l] + stride[l]*height[l] <= pyr_pitch. Only the
+ * width x height pixels of levels 1.. are written; row padding and the bytes between and behind
+ * the levels are left as they are and never influence a result. The kernels may LOAD bytes they
+ * do not use: the padding of a row, and up to 4 bytes before and behind a row's pixels inside
+ * [level_offset[l], level_offset[l] + stride[l]*height[l] + 4). Nothing behind
+ * pyr + n_images*pyr_pitch is ever read: a level from which another one is built and whose last
+ * row ends fewer than 4 bytes before pyr_pitch without row padding (stride[l] < width[l] + 4) is
+ * allowed, and the strips at the end of its last rows are then built byte by byte (a little
+ * slower; 4 spare bytes in the pitch, or 4 bytes of row padding, avoid that).
  */
 int dsdtm_pyrdown_batch_device(dsdtm_ctx* ctx, uint8_t* pyr, size_t pyr_pitch, int n_images,
                                int levels, const int* width, const int* height,

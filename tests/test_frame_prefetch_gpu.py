@@ -73,7 +73,7 @@ def make_image(width, height, seed):
 
 # ---- 1. every way the image can arrive ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("width,height", [(640, 480), (636, 478)])
-def test_every_way_the_image_can_arrive_gives_the_frame_of_create_from_image(gpu_ctx, width, height):
+def test_every_way_the_image_can_arrive_gives_the_frame_of_create_from_image(gpu_ctx, oracle, width, height):
     """Pageable (staged in the prefetch ring), pinned and 16-byte aligned (read in place by the ingest kernel), pinned at an odd
     address (the copy engine), row-strided (pageable and pinned: packed into the ring), device-resident (in place; strided: a
     device-to-device copy). 636 x 478: the byte count is no multiple of 16 (the kernel's byte tail) and the level widths are
@@ -85,6 +85,10 @@ def test_every_way_the_image_can_arrive_gives_the_frame_of_create_from_image(gpu
     ref = capi.DeviceFrame.from_image(gpu_ctx, img, LEVELS)
     want = pyramid_levels(ref, width, height)
     assert np.array_equal(want[0], img)
+    chain = [img]
+    for _ in range(1, LEVELS):
+        chain.append(oracle.pyrdown(chain[-1]))
+    assert same_pyramid(want, chain), "the pyramid of create_from_image is not the oracle's chain"
     pin = torch.empty(n + 64, dtype=torch.uint8).pin_memory()
     pin_s = torch.empty(height * (width + 24), dtype=torch.uint8).pin_memory()
     flat = pin.numpy()

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from dsdtm_amd import capi
+from tests import pyrdown_cases as PC
 
 pytestmark = pytest.mark.gpu
 
@@ -60,3 +61,39 @@ def test_batched_pyramids_match_the_oracle(gpu_ctx_each, oracle, shape, levels, 
                 assert np.array_equal(got[i][l], want[i][l]), f"{env}: image {i} level {l}"
         # nothing is written behind the last level
         assert not tail.any(), f"{env}: bytes behind the pyramid were written"
+
+
+# ---- the caller's layouts (tests/pyrdown_cases.py) ----------------------------------------------------------------------
+@pytest.mark.parametrize("name", PC.NAMES)
+def test_caller_layouts_match_the_oracle_and_leave_every_other_byte(gpu_ctx_each, oracle, name):
+    """Row padding, offsets that are 4 and 1 modulo 16, levels out of order, a source level that ends at the pitch, every
+    width class of the strip code, heights from 1 row on: levels 1.. equal the oracle's chain byte for byte, and every byte
+    the call may not write — level 0, padding (poisoned, with 0x00 / 0xFF next to level 0's rows), the gaps between the
+    levels, the bytes behind the last level and behind the last image — is what was uploaded. The release library's own
+    choice of kernel (128x288_L5_packed: pyrdown_fused_kernel<4> with 256 threads); then every variant on the diagnostic
+    one. That no load goes behind pyr + n * pitch (the `reversed` and `mid_last` layouts) rests on the code, not on this
+    run: the buffer has spare bytes behind the last image."""
+    import contextlib
+    import torch
+    gpu_ctx = gpu_ctx_each
+    b = PC.build(name)
+    c = b.case
+    want = PC.expected(oracle, name)
+    wa, ha, sa = (C.c_int * c.levels)(*b.ws), (C.c_int * c.levels)(*b.hs), (C.c_int * c.levels)(*b.strides)
+    oa = (C.c_size_t * c.levels)(*b.offs)
+    F = {"pyr_fused": 2}
+    envs = ({}, F, dict(F, pyr_band=2), dict(F, pyr_band=7), dict(F, pyr_band=100000), {"pyr_fused": 0}) if gpu_ctx.diag else ({},)
+    for env in envs:
+        dev = torch.from_numpy(b.host.copy()).to("cuda:0")
+        assert dev.data_ptr() % 16 == 0 and dev.numel() == b.base_shift + c.n * b.pitch + PC.SPARE
+        with (capi.debug_options(**env) if env else contextlib.nullcontext()):
+            st = torch.cuda.current_stream()
+            gpu_ctx.check(gpu_ctx.lib.dsdtm_pyrdown_batch_device(gpu_ctx.handle, dev.data_ptr() + b.base_shift, b.pitch, c.n, c.levels,
+                                                                wa, ha, sa, oa, st.cuda_stream))
+            torch.cuda.synchronize()
+        got = dev.cpu().numpy()
+        for i in range(c.n):
+            for l in range(1, c.levels):
+                assert np.array_equal(b.level(got, i, l), b.level(want, i, l)), f"{env}: image {i} level {l}"
+        changed = np.nonzero((got != b.host) & ~b.writable)[0]
+        assert changed.size == 0, f"{env}: {changed.size} bytes outside levels 1.. were written, the first at {changed[0]}"
