@@ -1,11 +1,14 @@
 // api_internal.h — what the host files of libdsdtm_amd.so share: the context and the few functions one host file calls in
-// another (namespace dsdtm::detail). api.cpp holds every stage but local BA (api_local_ba.cpp); a stage that moves into a file
-// of its own brings the names it needs here. Everything else is `static` in its own file. Not included by any kernel.
+// another (namespace dsdtm::detail), the small types they pass and the per-call helpers (inline). api.cpp holds every stage but the
+// tracked-frame entries (api_track.cpp) and local BA (api_local_ba.cpp); a stage that moves into a file of its own brings the names
+// it needs here. What one file alone uses is `static` there. Not included by any kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "../../include/dsdtm_amd.h"
@@ -130,8 +133,125 @@ void set_err(dsdtm_ctx* ctx, const char* fmt, ...);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// HIP_TRY for entries that own something until they succeed: answered by the enclosing `fail` lambda (which waits for what was enqueued and releases it)
+#define API_TRY(call)                                                                                          \
+    do {                                                                                                       \
+        hipError_t e_ = (call);                                                                                \
+        if (e_ != hipSuccess) { set_err(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return fail(DSDTM_ERR_HIP); } \
+    } while (0)
+
+// A pyramid as it lies on the device: dense rows, every level at a 64-byte aligned offset
+struct PackedPyr {
+    int levels;
+    int w[DSDTM_MAX_LEVELS], h[DSDTM_MAX_LEVELS];
+    size_t off[DSDTM_MAX_LEVELS];
+    size_t bytes;
+};
+
+// How a launch is accounted for (see dsdtm_ctx::h_flags / Recover)
+struct LaunchMode {
+    bool one_cu = false;        // never a team / two-member kernel (re-runs after a timeout, captured launches)
+    bool single = false;        // synchronous single-pair entry: its own timeout word, settled by the caller itself
+    int variant = -1;           // >= 0: this register variant, whatever max_features (dsdtm_track_frames: max_features is a stride)
+    const uint8_t* const* ref_ptrs = nullptr;   // device table of the pairs' reference pyramids (dsdtm_track_frames)
+    const uint8_t* const* cur_ptrs = nullptr;   // ... and of their current pyramids (resident frames; with ref_ptrs only)
+};
+
+// The frames of one dsdtm_track_frames call share one allocation (a slab: frame i at i * pitch, so that the batch kernels
+// address them as packed pyramids); the slab is released when its last frame is destroyed.
+struct FrameSlab {
+    dsdtm_ctx* owner;
+    int device;
+    uint8_t* d;
+    size_t bytes;
+    std::atomic<int> refs;
+};
+
+// How level 0 of a caller's gray image reaches the device (dsdtm_track_frame, dsdtm_track_frames, dsdtm_frame_prefetch):
+//   STAGED        packed into pinned memory of the entry's own (the caller does, and sets `dev` to its device alias), then as IN_PLACE
+//   IN_PLACE      read by ingest_kernel (pyrdown.hip) at `dev`: contiguous, 16-byte aligned, in this device's memory or in pinned
+//                 memory the device can address (a pinned image counts as pinned only when it is contiguous: a strided one is staged)
+//   COPY_D2D      a strided or odd-address image in this device's memory: hipMemcpy2DAsync
+//   COPY_H2D      a pinned image at an odd address, or one the device cannot address: hipMemcpyAsync
+//   OTHER_DEVICE  refused, in each entry's own words; `device`: where the image lives
+enum ImageRouteKind { STAGED, IN_PLACE, COPY_D2D, COPY_H2D, OTHER_DEVICE };
+struct ImageRoute { ImageRouteKind route; const void* dev; int device; };
+// What rides with the first ingest launch of a tracked call: Run's inputs and in/out words, pinned -> device
+struct RunRange { const void* src; void* dst; size_t bytes; };
+
+}  // namespace detail
+}  // namespace dsdtm
+
+struct dsdtm_frame {
+    dsdtm_ctx* owner;    // compared only, never dereferenced through the frame (a frame may outlive its context)
+    int device;
+    uint8_t* d;          // packed pyramid (the layout of plan_pyramid), its own allocation or a place in `slab`
+    size_t pitch;        // of the packed pyramid
+    dsdtm::detail::PackedPyr pl;
+    dsdtm::detail::FrameSlab* slab = nullptr;
+    size_t bytes = 0;    // of its own allocation (the pool's size key): the pyramid and, behind it, the depth plane
+    float* depth = nullptr;          // pl.w[0] x pl.h[0] floats, metres (dsdtm_frame_prefetch with a depth map), inside the allocation
+    unsigned long long seq = 0;      // dsdtm_frame_prefetch: the frame's number on the prefetch stream; 0: never pending
+};
+// tests/test_frame_prefetch_gpu.py reads a frame's pyramid back through these first members (it has no public entry to do so):
+// a change of their layout must fail here, not there
+static_assert(offsetof(dsdtm_frame, owner) == 0 && offsetof(dsdtm_frame, device) == 8 && offsetof(dsdtm_frame, d) == 16 &&
+              offsetof(dsdtm_frame, pitch) == 24, "struct dsdtm_frame: update _FrameHead in tests/test_frame_prefetch_gpu.py");
+
+namespace dsdtm {
+namespace detail {
+
+// api.cpp defines these; api_track.cpp calls them (ensure_stage: api_local_ba.cpp too)
 // The pinned staging block and the device one, each grown to `bytes` (never shrunk)
 int ensure_stage(dsdtm_ctx* ctx, size_t bytes);
+int pinned_device_ptr(dsdtm_ctx* ctx, uint8_t** p);
+void plan_image_pyramid(int width, int height, int levels, PackedPyr* pl, int st[]);
+uint8_t* pool_take(dsdtm_ctx* ctx, size_t bytes, unsigned long long* seq);
+bool pool_give(dsdtm_ctx* ctx, dsdtm_ctx* owner, int device, uint8_t* d, size_t bytes, unsigned long long seq = 0);
+int validate_params(dsdtm_ctx* ctx, const dsdtm_align_params* p, int levels);
+int launch_batch(dsdtm_ctx* ctx, const dsdtm_batch_desc* b, const dsdtm_camera* cam, const dsdtm_align_params* prm,
+                 void* hip_stream, const LaunchMode& mode, bool* multi_cu_used);
+void clear_stream_counters(dsdtm_ctx* ctx, hipStream_t stream);
+int frame_alloc(dsdtm_ctx* ctx, const PackedPyr& pl, hipStream_t stream, dsdtm_frame** out, bool with_depth = false);
+ImageRoute route_image(dsdtm_ctx* ctx, const void* ptr, int width, int stride, bool clear_unaligned, const int* known_mem = nullptr);
+int enqueue_level0(dsdtm_ctx* ctx, const ImageRoute& r, const uint8_t* image, int width, int height, int stride, uint8_t* dst,
+                   const RunRange* run, hipStream_t stream);
+
+// The per-call helpers: inline, so that a call from another file costs what it cost inside api.cpp
+
+// `rows` rows of row_bytes from one pitch to another (one memcpy where both are dense)
+inline void copy_rows(void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t row_bytes, size_t rows) {
+    if (dst_stride == row_bytes && src_stride == row_bytes) { memcpy(dst, src, row_bytes * rows); return; }
+    for (size_t y = 0; y < rows; ++y) memcpy((uint8_t*)dst + y * dst_stride, (const uint8_t*)src + y * src_stride, row_bytes);
+}
+
+// the level table of a batch / image descriptor whose pyramids are packed
+template <class Desc>
+inline void fill_levels(Desc& b, const PackedPyr& pl) {
+    b.levels = pl.levels;
+    for (int l = 0; l < pl.levels; ++l) { b.width[l] = pl.w[l]; b.height[l] = pl.h[l]; b.stride[l] = pl.w[l]; b.level_offset[l] = pl.off[l]; }
+}
+// ... and the first `levels` levels of a packed pyramid as the kernels take them
+inline void fill_levels(LevelGeom* lv, const PackedPyr& pl, int levels) {
+    for (int l = 0; l < levels; ++l) { lv[l].w = pl.w[l]; lv[l].h = pl.h[l]; lv[l].stride = pl.w[l]; lv[l].off = (uint32_t)pl.off[l]; }
+}
+
+// A frame that dsdtm_frame_prefetch handed out may still be on its way: before `stream` reads frames numbered up to `seq`
+// it waits for the event behind that number — on the device, never on the host. Nothing to do once the host knows the
+// frame to be resident (prefetch_settled), or when the context's stream has already been told to wait that far.
+inline int frames_consume(dsdtm_ctx* ctx, unsigned long long seq, hipStream_t stream) {
+    if (seq <= ctx->prefetch_settled || stream == ctx->prefetch_stream) return DSDTM_OK;
+    if (stream == ctx->stream && seq <= ctx->prefetch_waiting) return DSDTM_OK;
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->prefetch_event[seq % dsdtm_ctx::PREFETCH_EVENTS], 0));
+    if (stream == ctx->stream) ctx->prefetch_waiting = seq;
+    return DSDTM_OK;
+}
+// behind a host synchronisation of the context's stream: what it was told to wait for has arrived.
+// INVARIANT: called only after hipStreamSynchronize(ctx->stream) has returned success — never behind a wait for another
+// stream or for an event: prefetch_waiting counts the waits enqueued on ctx->stream alone (frames_consume).
+inline void frames_settle(dsdtm_ctx* ctx) {
+    if (ctx->prefetch_waiting > ctx->prefetch_settled) ctx->prefetch_settled = ctx->prefetch_waiting;
+}
 
 }  // namespace detail
 }  // namespace dsdtm

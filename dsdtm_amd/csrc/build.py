@@ -27,7 +27,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["api.cpp", "api_local_ba.cpp",   # the host side, over api_internal.h
+SOURCES = ["api.cpp", "api_track.cpp", "api_local_ba.cpp",   # the host side, over api_internal.h
            "sparse_align.hip", "align2d.hip", "pyrdown.hip", "warp.hip", "match.hip", "detect.hip", "pose_opt.hip", "track.hip", "local_ba.hip", "rgbd.hip"]
 DIAG_SOURCES = ["selftest.hip"]                      # diagnostic build only
 HEADERS = ["api_internal.h", "kernels.h", "device_math.h", "warp_body.h", "align2d_body.h", "match_body.h", "pose_math.h", "exports.map", os.path.join("..", "..", "include", "dsdtm_amd.h")]

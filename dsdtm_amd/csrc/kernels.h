@@ -1,4 +1,4 @@
-// kernels.h — launch-side declarations shared by the .hip kernels and api.cpp.
+// kernels.h — launch-side declarations shared by the .hip kernels and the host files (api.cpp, api_*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

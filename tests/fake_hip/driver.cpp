@@ -1,9 +1,9 @@
-// tests/fake_hip/driver.cpp — scenarios that drive the HOST side of the C ABI (dsdtm_amd/csrc/api.cpp: stream rings, pair
+// tests/fake_hip/driver.cpp — scenarios that drive the HOST side of the C ABI (dsdtm_amd/csrc/api.cpp, api_*.cpp: stream rings, pair
 // counters, recover slots, the team epoch, the sharded / streamed entries, frames, the single-call entries' packing) against the
 // fake HIP runtime, under AddressSanitizer + UBSan (or ThreadSanitizer for the two-thread scenario). TEST INFRASTRUCTURE ONLY.
 //   usage: driver [--trace] [scenario ...]   (no scenario: all of them); prints "ok <name>" per scenario, exits non-zero on failure
 //   --trace: behind every scenario, the call counts, copies (kind, bytes) and launch log it left (fake_hip_print_trace) — two
-//   builds of api.cpp that print the same trace make the same calls in the same order with the same sizes
+//   builds of the host files that print the same trace make the same calls in the same order with the same sizes
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>

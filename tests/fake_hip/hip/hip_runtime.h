@@ -1,10 +1,10 @@
 // tests/fake_hip/hip/hip_runtime.h — a FAKE HIP runtime header for the CPU sanitizer job (tests/test_fake_hip_cpu.py).
-// TEST INFRASTRUCTURE ONLY: dsdtm_amd/csrc/api.cpp (the host side of the C ABI: stream rings, pair counters, recover slots,
+// TEST INFRASTRUCTURE ONLY: dsdtm_amd/csrc/api.cpp, api_*.cpp (the host side of the C ABI: stream rings, pair counters, recover slots,
 // the sharded / streamed entries, frames) is compiled against THIS header with g++ -fsanitize=address,undefined (or thread)
 // and linked with fake_hip.cpp, which keeps "device" memory in the host heap, queues every asynchronous operation per
 // stream and executes it only when something waits for it — so a copy whose source or destination was freed too early, a
 // record that points into a regrown staging buffer, or a launch accounted to the wrong stream shows up on the CPU.
-// Nothing here is used by the product; the names and signatures are the subset of HIP that api.cpp and kernels.h use.
+// Nothing here is used by the product; the names and signatures are the subset of HIP that the host files and kernels.h use.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -160,7 +160,7 @@ static bool batch_failures() {
 // reach its slot of the slab, and Run's range must reach the device exactly once — with the first slot's ingest launch, or with a
 // launch of its own where the first slot travels by the copy engine
 enum Arrival { DEV_STRIDED, PAGEABLE, PAGEABLE_STRIDED, PINNED, PINNED_ODD, DEV };
-struct FrameHead { void* owner; int device; uint8_t* d; };      // the first members of dsdtm_frame (api.cpp asserts their layout)
+struct FrameHead { void* owner; int device; uint8_t* d; };      // the first members of dsdtm_frame (api_internal.h asserts their layout)
 static uint8_t pixel(int f, int x, int y) { return (uint8_t)(x * 3 + y * 7 + f * 31 + 1); }
 struct Arrivals {
     int nf = 0;

@@ -11,7 +11,7 @@ from dsdtm_amd.csrc import build as hip_build
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = os.path.join(ROOT, "tests", "fake_hip")
 CSRC = os.path.join(ROOT, "dsdtm_amd", "csrc")
-# The host files of libdsdtm_amd.so that every `api` driver links: all of them (today api.cpp) but the local-BA one, whose launches
+# The host files of libdsdtm_amd.so that every `api` driver links: all of them (api.cpp, api_track.cpp) but the local-BA one, whose launches
 # no driver fakes and whose entries no driver calls
 API_SOURCES = [s for s in hip_build.SOURCES if s.endswith(".cpp") and s != "api_local_ba.cpp"]
 COMMON_FLAGS = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wno-unused-function", "-pthread"]

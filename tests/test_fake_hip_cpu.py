@@ -1,6 +1,6 @@
 """The HOST side of the C ABI under sanitizers, without a GPU (round-5 verdict, item 4).
 
-dsdtm_amd/csrc/api.cpp — stream rings and pair counters, recover slots, the team ring's tag epoch, the sharded / streamed
+dsdtm_amd/csrc/api.cpp and api_*.cpp — stream rings and pair counters, recover slots, the team ring's tag epoch, the sharded / streamed
 entries, frames and their buffer pool, the staging blocks every single-call entry and dsdtm_track_frame pack — is compiled with
 g++ against a FAKE HIP runtime (tests/fake_hip/: "device" memory in the host heap; every asynchronous operation queued and run
 only when something waits for it; fake kernel launchers that touch every buffer a launch names, check the invariants the real

@@ -47,7 +47,7 @@ def _hip():
 
 
 class _FrameHead(C.Structure):
-    """The first members of struct dsdtm_frame (dsdtm_amd/csrc/api.cpp): owner, device, d (the packed pyramid), pitch."""
+    """The first members of struct dsdtm_frame (dsdtm_amd/csrc/api_internal.h): owner, device, d (the packed pyramid), pitch."""
     _fields_ = [("owner", C.c_void_p), ("device", C.c_int), ("d", C.c_void_p), ("pitch", C.c_size_t)]
 
 

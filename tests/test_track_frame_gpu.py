@@ -197,7 +197,7 @@ def test_tracked_sequence_one_call_per_frame_equals_the_four_call_chain(gpu_ctx)
 
 @pytest.mark.parametrize("width,height", [(640, 480), (636, 478)])
 def test_every_way_the_image_can_arrive_gives_the_same_frame(gpu_ctx, width, height):
-    """Level 0 reaches the device on several paths (api.cpp, dsdtm_track_frame step 1): a pageable image is staged through the context's
+    """Level 0 reaches the device on several paths (api_track.cpp, dsdtm_track_frame step 1): a pageable image is staged through the context's
     pinned block and read from there by ingest_kernel; a pinned, 16-byte aligned image is read by that kernel straight from the
     caller's buffer; a pinned image at an odd address goes through the copy engine; a row-strided image is packed row by row first; an image
     in device memory is read where it is, or copied device to device when it is strided or at an odd address.
