@@ -49,6 +49,10 @@ ADDONS = {
     "homography": (["homography_api.cpp", "homography.hip"],
                    ["homography.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_homography.h"), os.path.join(_INC, "dsdtm_amd.h")],
                    os.path.join(HERE, "libdsdtm_amd_homography.so")),
+    # include/dsdtm_amd_localmap.h: the device-resident map and the selection of Tracking::UpdateLocalMap / GetCloseKeyFrames
+    "localmap": (["localmap_api.cpp", "localmap.hip"],
+                 ["localmap.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_localmap.h"), os.path.join(_INC, "dsdtm_amd.h")],
+                 os.path.join(HERE, "libdsdtm_amd_localmap.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")

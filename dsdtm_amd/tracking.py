@@ -300,6 +300,28 @@ class Tracker:
         dsdtm_keyframe_verdict). Reads the objects only: TrackFrame's results are untouched."""
         return capi.need_keyframe(self.ctx, self.cam, params or self.keyframe_params(), keyframe_desc(cur, last_kf, local_keyframes))
 
+    def UpdateLocalMap(self, store, T, n_local: int = 10):
+        """The keyframe and point selection of Tracking::UpdateLocalMap (src/Tracking.cpp:258-297, GetCloseKeyFrames included) for
+        the pose T on `store` (a local_map.LocalMapStore: the map on the device), through dsdtm_localmap_select. Returns
+        (keyframes, map_points) as TrackFrame takes them: map_points in the order the reference hands them to ReprojectPoint;
+        keyframes = every keyframe of the store in index order, because a map point's mObservations are keyed by that index and
+        Get_ClosetObs walks all of them, local or not. mvpLocalKeyFrames (what NeedKeyframe takes) is kept in
+        self.local_keyframes. Measured (profiles/r17_local_map.txt): the device select is 140-190 us whatever the map; below about
+        170 keyframes the host evaluation (select_local_map_host, 0.9 us per keyframe) is the faster call for one pose, above it
+        this one (5.8x at 1000 keyframes); MultiTracker.UpdateLocalMaps with 64 sequences or more wins from 100 keyframes on."""
+        (self.local_keyframes, map_points), = _select_local_maps(self.cam, [store], [T], n_local)
+        return list(store.keyframes), map_points
+
+
+def _select_local_maps(cam, stores, Ts, n_local):
+    """[(mvpLocalKeyFrames, local map points)] for n stores of ONE local_map.LocalMapContext, in one dsdtm_localmap_select."""
+    from . import local_map
+    if not stores:
+        return []
+    if any(s.ctx is not stores[0].ctx for s in stores):
+        raise ValueError("the stores of one call share one LocalMapContext")
+    return local_map.update_local_maps(stores[0].ctx, cam, stores, Ts, n_local)
+
 
 class MultiTracker:
     """Tracker.TrackFrame for n independent sequences at once (a multi-camera rig, offline re-tracking, many robots): one
@@ -369,3 +391,11 @@ class MultiTracker:
             raise ValueError(f"{len(curs)} frames, {len(last_kfs)} last keyframes, {len(local_keyframes)} local keyframe lists")
         descs = [keyframe_desc(c, k, lk) for c, k, lk in zip(curs, last_kfs, local_keyframes)]
         return capi.need_keyframes(self.ctx, self.cam, params or self.t.keyframe_params(), descs)
+
+    def UpdateLocalMaps(self, stores, Ts, n_local: int = 10):
+        """Tracker.UpdateLocalMap for the n sequences of a step in ONE dsdtm_localmap_select (stores of one
+        local_map.LocalMapContext; a rig's sequences may share a store). Returns (keyframes, map_points), each a list of n, as
+        TrackFrames takes them; self.local_keyframes[i] is sequence i's mvpLocalKeyFrames."""
+        picked = _select_local_maps(self.cam, list(stores), list(Ts), n_local)
+        self.local_keyframes = [lk for lk, _ in picked]
+        return [list(s.keyframes) for s in stores], [mps for _, mps in picked]
