@@ -53,6 +53,11 @@ ADDONS = {
     "localmap": (["localmap_api.cpp", "localmap.hip"],
                  ["localmap.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_localmap.h"), os.path.join(_INC, "dsdtm_amd.h")],
                  os.path.join(HERE, "libdsdtm_amd_localmap.so")),
+    # include/dsdtm_amd_trackmap.h: the resident track map and dsdtm_track_desc's local-map columns (the selection is localmap.hip's)
+    "trackmap": (["trackmap_api.cpp", "trackmap.hip", "localmap.hip"],
+                 ["trackmap.h", "localmap.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_trackmap.h"),
+                  os.path.join(_INC, "dsdtm_amd_localmap.h"), os.path.join(_INC, "dsdtm_amd.h")],
+                 os.path.join(HERE, "libdsdtm_amd_trackmap.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")
