@@ -55,9 +55,15 @@ ADDONS = {
                  os.path.join(HERE, "libdsdtm_amd_localmap.so")),
     # include/dsdtm_amd_trackmap.h: the resident track map and dsdtm_track_desc's local-map columns (the selection is localmap.hip's)
     "trackmap": (["trackmap_api.cpp", "trackmap.hip", "localmap.hip"],
-                 ["trackmap.h", "localmap.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_trackmap.h"),
+                 ["trackmap_api_body.h", "trackmap.h", "localmap.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_trackmap.h"),
                   os.path.join(_INC, "dsdtm_amd_localmap.h"), os.path.join(_INC, "dsdtm_amd.h")],
                  os.path.join(HERE, "libdsdtm_amd_trackmap.so")),
+    # include/dsdtm_amd_mapping.h: the same resident map (trackmap_api_body.h compiled under the dsdtm_mapping_* names) and the mapping
+    # thread's covisibility list, local-BA window and commit
+    "mapping": (["mapping_api.cpp", "mapping.hip", "trackmap.hip", "localmap.hip"],
+                ["mapping.h", "trackmap_api_body.h", "trackmap.h", "localmap.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_mapping.h"),
+                 os.path.join(_INC, "dsdtm_amd_trackmap.h"), os.path.join(_INC, "dsdtm_amd_localmap.h"), os.path.join(_INC, "dsdtm_amd.h")],
+                os.path.join(HERE, "libdsdtm_amd_mapping.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")

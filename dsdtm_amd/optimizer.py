@@ -132,6 +132,47 @@ class Optimizer:
         Optimizer.last_summary = sm
         return sm
 
+    @staticmethod
+    def LocalBundleAdjustmentOnDevice(mctx, dmap, kf: int, cov_kf, origin_kf: int = -1, delta: float | None = None, ctx: capi.Context | None = None,
+                                      capacities=(capi.LBA_MAX_FREE_KF + capi.LBA_MAX_CONST_KF, capi.LBA_MAX_POINTS, capi.LBA_MAX_OBSERVATIONS),
+                                      max_iterations: int = 10, bad_capacity: int = 256, mf: float = 1.0):
+        """src/Optimizer.cpp:103-282 on a map that is resident on the device (include/dsdtm_amd_mapping.h): window ->
+        dsdtm_local_ba_batch_device -> commit, with no column crossing the link. mctx: a ba_window.MappingContext; dmap: its map;
+        kf, cov_kf, origin_kf: map indices (cov_kf = the keyframe's stored GetCovKFrames(), normally what dsdtm_mapping_covisibility
+        returned when it was created). delta None: double(float Optimization.LocalBAthreshhold) / float mf (:105-106).
+        Returns None when the window is not usable — the caller takes LocalBundleAdjustment above, the host path, for that keyframe —
+        else a dict: window (counts, flags, kf_index / point_index / obs_slot for the bookkeeping on the host's objects), outlier
+        (the solver's flags per observation), summary, commit (n_outliers, n_bad, overflow_bad, bad_points: map indices)."""
+        import torch
+        from . import ba_window
+        if delta is None:
+            delta = float(np.float32(Config.Get("Optimization.LocalBAthreshhold"))) / float(np.float32(mf))
+        ctx = ctx or capi.default_context()
+        call = ba_window.WindowCall(mctx, [(dmap, kf, cov_kf, origin_kf, *capacities)])
+        win = call.run()[0]
+        if not win["usable"]:
+            return None
+        t = call.tensors
+        outlier = torch.zeros(max(call.total["obs"], 1), dtype=torch.uint8, device=t["T_c2w"].device)
+        summary = torch.zeros(capi.LBA_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=t["T_c2w"].device)
+        prm = capi.LocalBaParams(int(max_iterations), 0, float(delta))
+        # (a prototype of its own: the library handle's shared function object is left as other callers set it)
+        proto = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, *([C.c_void_p] * 7), C.POINTER(capi.LocalBaParams), C.c_void_p, C.c_void_p, C.c_void_p)
+        f = proto(("dsdtm_local_ba_batch_device", ctx.lib))
+        stream = torch.cuda.current_stream()
+        ctx.check(f(ctx.handle, 1, C.cast(call.problems, C.c_void_p), t["T_c2w"].data_ptr(), t["kf_constant"].data_ptr(), t["points"].data_ptr(),
+                    t["obs_kf"].data_ptr(), t["obs_point"].data_ptr(), t["obs_bearing"].data_ptr(), t["obs_level"].data_ptr(), C.byref(prm),
+                    outlier.data_ptr(), summary.data_ptr(), C.c_void_p(stream.cuda_stream)))
+        # (no wait here: the commit orders itself behind the solve on the device)
+        st, res = call.commit(outlier, C.c_void_p(stream.cuda_stream), bad_capacity)
+        mctx.check(st)
+        sm = np.frombuffer(summary.cpu().numpy().tobytes(), capi.LBA_SUMMARY_DTYPE)[0]
+        nk, npt = win["n_local"] + win["n_fixed"], win["n_points"]
+        out = dict(window=win, outlier=outlier[:win["n_obs"]].cpu().numpy(), summary={k: sm[k].item() for k in sm.dtype.names}, commit=res[0],
+                   T_c2w=call.column("T_c2w")[:nk].copy(), points=call.column("points")[:npt].copy())
+        Optimizer.last_summary = out["summary"]
+        return out
+
 
 def pose_optimization(ctx: capi.Context, bearing, p_world, level, use, T_cur_w, max_iterations: int = 100):
     """dsdtm_pose_optimization: T_cur_w (12 doubles) is updated in place; returns (residual norms in
