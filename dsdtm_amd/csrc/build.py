@@ -64,6 +64,10 @@ ADDONS = {
                 ["mapping.h", "trackmap_api_body.h", "trackmap.h", "localmap.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_mapping.h"),
                  os.path.join(_INC, "dsdtm_amd_trackmap.h"), os.path.join(_INC, "dsdtm_amd_localmap.h"), os.path.join(_INC, "dsdtm_amd.h")],
                 os.path.join(HERE, "libdsdtm_amd_mapping.so")),
+    # include/dsdtm_amd_newkf.h: the walk and the lift of Tracking::CraeteKeyframe, from the per-cell corners to the keyframe's columns
+    "newkf": (["newkf_api.cpp", "newkf.hip"],
+              ["newkf.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_newkf.h"), os.path.join(_INC, "dsdtm_amd.h")],
+              os.path.join(HERE, "libdsdtm_amd_newkf.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")

@@ -278,6 +278,28 @@ class TrackMapStore:
         self.keyframes.append(kf)
         return k
 
+    def add_keyframe_columns(self, kf, new_points, point_of_slot, observes) -> int:
+        """add_keyframe from the columns dsdtm_newkf_make returned (keyframe_creation.create_keyframes): `new_points` are appended as
+        points [len(points), ...) in that order — the numbering point_of_slot was made with — and the keyframe's slots are written as
+        given, without a walk over the objects. The caller enters the observations into the points afterwards."""
+        first = len(self.points)
+        if any(id(mp) in self._point_index for mp in new_points):
+            raise ValueError("a new point is already in the map")
+        if new_points:
+            self.map.points_write(first, [mp.Get_Pose() for mp in new_points], [1 if mp.IsBad() else 0 for mp in new_points],
+                                  [mp.Get_FoundNums() for mp in new_points])
+        k = len(self.keyframes)
+        try:
+            got = self.map.keyframe_add(np.asarray(kf.Get_Pose(), np.float64).reshape(12), point_of_slot, observes, kf.px, kf.level, kf.bearing)
+        finally:
+            for mp in new_points:                           # (the points are in the device map whether or not the keyframe followed)
+                self._point_index[id(mp)] = len(self.points)
+                self.points.append(mp)
+        assert got == k
+        self._kf_index[id(kf)] = k
+        self.keyframes.append(kf)
+        return k
+
     def update_keyframe(self, kf, pose: bool = True, slots: bool = True):
         k = self._kf_index[id(kf)]
         if slots:
