@@ -61,13 +61,21 @@ ADDONS = {
     # include/dsdtm_amd_mapping.h: the same resident map (trackmap_api_body.h compiled under the dsdtm_mapping_* names) and the mapping
     # thread's covisibility list, local-BA window and commit
     "mapping": (["mapping_api.cpp", "mapping.hip", "trackmap.hip", "localmap.hip"],
-                ["mapping.h", "trackmap_api_body.h", "trackmap.h", "localmap.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_mapping.h"),
+                ["mapping.h", "mapping_api_body.h", "trackmap_api_body.h", "trackmap.h", "localmap.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_mapping.h"),
                  os.path.join(_INC, "dsdtm_amd_trackmap.h"), os.path.join(_INC, "dsdtm_amd_localmap.h"), os.path.join(_INC, "dsdtm_amd.h")],
                 os.path.join(HERE, "libdsdtm_amd_mapping.so")),
     # include/dsdtm_amd_newkf.h: the walk and the lift of Tracking::CraeteKeyframe, from the per-cell corners to the keyframe's columns
     "newkf": (["newkf_api.cpp", "newkf.hip"],
               ["newkf.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_newkf.h"), os.path.join(_INC, "dsdtm_amd.h")],
               os.path.join(HERE, "libdsdtm_amd_newkf.so")),
+    # include/dsdtm_amd_slam.h: the same resident map and the mapping entries (both bodies compiled under the dsdtm_slam_* names) and a
+    # tracked frame's effects on the map and the gather of the keyframe decision on it (aftertrack.hip; keyframe.hip is linked as it is)
+    "slam": (["slam_api.cpp", "aftertrack.hip", "mapping.hip", "trackmap.hip", "localmap.hip", "keyframe.hip"],
+             ["aftertrack.h", "mapping.h", "mapping_api_body.h", "trackmap_api_body.h", "trackmap.h", "localmap.h", "keyframe.h", "addon_host.h",
+              "device_math.h", "pose_math.h", "exports.map", os.path.join(_INC, "dsdtm_amd_slam.h"), os.path.join(_INC, "dsdtm_amd_mapping.h"),
+              os.path.join(_INC, "dsdtm_amd_trackmap.h"), os.path.join(_INC, "dsdtm_amd_localmap.h"), os.path.join(_INC, "dsdtm_amd_keyframe.h"),
+              os.path.join(_INC, "dsdtm_amd.h")],
+             os.path.join(HERE, "libdsdtm_amd_slam.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")

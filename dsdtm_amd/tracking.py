@@ -342,6 +342,16 @@ class Tracker:
         (self.local_keyframes, map_points), = _select_local_maps(self.cam, [store], [T], n_local)
         return list(store.keyframes), map_points
 
+    def CommitTrackedFrame(self, store, r, point_list):
+        """A tracked frame's effects on the RESIDENT map (IncreaseFound, the EraseFound walk, the SetBadFlag cascade: rules T1-T4 of
+        include/dsdtm_amd_slam.h) through dsdtm_slam_track_commit: what apply_tracked_frame did to the objects, on `store` (a
+        track_map.TrackMapStore over a slam.SlamContext), with no found_write / points_write / keyframe_write. `r`: the track_frame
+        result (TrackFrame keeps it in self.last_result); `point_list`: the `point` list store.local() returned for this frame.
+        Returns the entry's answer (n_erased, n_bad, bad_points, found_after, points). Measured (profiles/r21_aftertrack.txt): 25-44 us per
+        call; track_commit_host is faster unless a point goes bad on a map of more than about 200 keyframes."""
+        from . import slam
+        return slam.commit_tracked_frames(store.ctx, self.cam, [store], [r], [point_list])[0]
+
 
 def _select_local_maps(cam, stores, Ts, n_local):
     """[(mvpLocalKeyFrames, local map points)] for n stores of ONE local_map.LocalMapContext, in one dsdtm_localmap_select."""
@@ -438,3 +448,35 @@ class MultiTracker:
         picked = _select_local_maps(self.cam, list(stores), list(Ts), n_local)
         self.local_keyframes = [lk for lk, _ in picked]
         return [list(s.keyframes) for s in stores], [mps for _, mps in picked]
+
+    def NeedKeyframesOnMap(self, stores, curs, last_kfs, local_keyframes, params=None) -> list:
+        """NeedKeyframes on the RESIDENT map, in ONE dsdtm_slam_need_keyframes (stores of one slam.SlamContext): no position crosses the
+        link — each frame's map points go up as the store's point indices (feature order), the last keyframe and mvpLocalKeyFrames as
+        its keyframe indices; positions, bad flags, the keyframe's slots and the camera centres are read from the map. last_kfs[i] and
+        local_keyframes[i] are keyframe objects of stores[i]. Returns n verdict dicts, as NeedKeyframes does."""
+        if not (len(stores) == len(curs) == len(last_kfs) == len(local_keyframes)):
+            raise ValueError(f"{len(stores)} stores, {len(curs)} frames, {len(last_kfs)} last keyframes, {len(local_keyframes)} local keyframe lists")
+        if not stores:
+            return []
+        if any(s.ctx is not stores[0].ctx for s in stores):
+            raise ValueError("the stores of one call share one SlamContext")
+        trackers = []
+        for s, cur, kf, lks in zip(stores, curs, last_kfs, local_keyframes):
+            mc = frame_map_points(cur)
+            trackers.append(dict(map=s.map, T_cur_w=np.asarray(cur.Get_Pose(), np.float64).reshape(12), n_valid=len(mc), cur_point=[s.point_index(mp) for mp in mc],
+                                 kf=s.keyframe_index(kf), local_kf=[s.keyframe_index(k) for k in lks]))
+        return stores[0].ctx.need_keyframes(self.cam, params or self.t.keyframe_params(), trackers)
+
+    def CommitTrackedFrames(self, stores, point_lists, results=None) -> list:
+        """Tracker.CommitTrackedFrame for the n sequences of a step in ONE dsdtm_slam_track_commit (stores of one slam.SlamContext;
+        sequences that share a store are applied in list order, as the lockstep loop applies them). `results` defaults to
+        self.last_results. Returns n answers."""
+        from . import slam
+        results = self.last_results if results is None else results
+        if not (len(stores) == len(point_lists) == len(results)):
+            raise ValueError(f"{len(stores)} stores, {len(point_lists)} point lists, {len(results)} results")
+        if not stores:
+            return []
+        if any(s.ctx is not stores[0].ctx for s in stores):
+            raise ValueError("the stores of one call share one SlamContext")
+        return slam.commit_tracked_frames(stores[0].ctx, self.cam, list(stores), list(results), list(point_lists))
