@@ -145,10 +145,11 @@ def wide_pool():                                            # 10
 
 
 # ---- dsdtm_slam_need_keyframes: trackers of tests/need_keyframe_cases.py turned into maps -------------------------------------------
-def keyframe_world(c, holes=(), extra_kf=0):
+def keyframe_world(c, holes=(), extra_kf=0, slots=None):
     """A map that holds the tracker `c` of need_keyframe_cases: the last keyframe's points, then the current frame's; keyframe 0 is the
     last keyframe (pose T_kf; its slots list its points in order, with a -1 slot in front of every list position in `holes` and one at
-    the end); keyframes 1 .. are the local keyframes, at [I | -centre] (so that Get_CameraCnt is the centre, exactly), then `extra_kf`
+    the end — or, with `slots`, exactly that list: the position in c's kf list of the point each slot lists, ascending, or -1);
+    keyframes 1 .. are the local keyframes, at [I | -centre] (so that Get_CameraCnt is the centre, exactly), then `extra_kf`
     more. Returns (world, tracker): tracker has T_cur_w, n_valid, cur_point, kf, local_kf and params."""
     kf_p, cur_p = np.asarray(c["kf_p"], np.float64).reshape(-1, 3), np.asarray(c["cur_p"], np.float64).reshape(-1, 3)
     nk, nc = len(kf_p), len(cur_p)
@@ -161,6 +162,9 @@ def keyframe_world(c, holes=(), extra_kf=0):
             slots0.append(-1)
         slots0.append(i)
     slots0.append(-1)
+    if slots is not None:
+        slots0 = [int(p) for p in slots]
+        assert [p for p in slots0 if p >= 0] == list(range(nk))
     lkf = np.asarray(c["lkf"], np.float64).reshape(-1, 3)
     poses = [np.asarray(c["T_kf"], np.float64).reshape(12)]
     for ctr in list(lkf) + [np.array([9.0, 9.0, 9.0])] * extra_kf:
@@ -178,9 +182,55 @@ def keyframe_world(c, holes=(), extra_kf=0):
     return world, tracker
 
 
+ROUND = 256                             # the slots the gather kernel compacts per round
+
+
+def long_keyframe(slots_of, n_slots):
+    """A tracker of need_keyframe_cases whose last keyframe has n_slots slots: slots_of maps a slot to ("good", displacement in px) or
+    ("bad", displacement); every other slot is -1. The current camera stands 8/512 beside the keyframe's and looks along +z, so a point
+    (0, 0, z) is displaced by 8 / z px between the two images. Returns (case, slots)."""
+    from dsdtm_amd.keyframe_decision import KeyframeParams
+    from tests import need_keyframe_cases as NK
+    kf_p, kf_bad, slots = [], [], []
+    for s in range(n_slots):
+        if s in slots_of:
+            kind, px = slots_of[s]
+            slots.append(len(kf_p))
+            kf_p.append([0.0, 0.0, 8.0 / px])
+            kf_bad.append(int(kind == "bad"))
+        else:
+            slots.append(-1)
+    return NK.make(T_cur=NK.pose(8.0 / 512.0), kf_p=kf_p, kf_bad=kf_bad, params=KeyframeParams(min_trans=1.0)), slots
+
+
+def long_keyframe_cases():
+    """The last keyframes past one round of the gather's slot-order compaction. K2 samples the first 31 good points in slot order, so
+    each world makes the verdict depend on the later rounds (tests/test_aftertrack_cpu.py holds them to that)."""
+    out = {}
+    out["kf_256_slots"] = {s: ("good", 8.0 + s) for s in range(256)}              # one full round, no second: sample 31 is slot 30
+    w = {}                                                                          # slots 0..255: 30 good (15 at 8 px, 15 at 4096 px), 30 bad, holes
+    for i in range(30):
+        w[8 * i] = ("good", 8.0 if i % 2 == 0 else 4096.0)
+        w[8 * i + 4] = ("bad", 64.0)
+    w[256] = ("good", 128.0)                                                        # the 31st sample, and the median
+    out["kf_257_slots_31st_sample_in_round_two"] = w
+    w = {s: ("bad", 16.0 + s) for s in range(512) if s % 5 == 2 or s in (254, 257, 510)}      # (255, 256 and 511, 512 stay -1)
+    w.update({520 + 2 * i: ("good", 32.0 + i) for i in range(40)})
+    out["kf_600_slots_all_samples_from_round_three"] = w
+    w = {3 + 20 * i: ("good", 8.0) for i in range(10)}                              # round one: 10 good, 40 bad
+    w.update({4 + 6 * i: ("bad", 2048.0) for i in range(40)})
+    for lane in range(64):                                                          # round two: wavefront 1 (5 good among bad), wavefront 3 (64 good)
+        w[ROUND + 64 + lane] = ("good", 64.0 + lane) if lane in (3, 17, 31, 45, 63) else ("bad", 2048.0)
+        w[ROUND + 192 + lane] = ("good", 256.0 + lane)
+    out["kf_round_two_waves_1_and_3_only"] = w
+    return {name: long_keyframe(w, {"kf_256_slots": 256, "kf_257_slots_31st_sample_in_round_two": 257, "kf_600_slots_all_samples_from_round_three": 600,
+                                    "kf_round_two_waves_1_and_3_only": 512}[name]) for name, w in out.items()}
+
+
 def keyframe_cases():
     """(name, world, tracker): one per deciding rule K1..K4; the 40-slot keyframe with -1 and bad slots mixed in (the 31-sample cut);
-    bad points in the cur list; empty lists; 0 and 64 local keyframes; 4096 cur points; a point at z = 0 (undefined)."""
+    bad points in the cur list; empty lists; 0 and 64 local keyframes; 4096 cur points; a point at z = 0 (undefined); and the long last
+    keyframes of long_keyframe_cases (256, 257, 600 and 512 slots: one, two and three rounds of the gather's compaction)."""
     from tests import need_keyframe_cases as NK
 
     def make():
@@ -204,13 +254,16 @@ def keyframe_cases():
         add("64_local_keyframes_last_fires", NK.random_case(8, 25, 40, 64, bad="some", fire=63))
         add("4096_cur_points", NK.random_case(9, 4096, 50, 4, bad="some", fire=2))
         add("a_point_at_z_0_is_undefined", NK.make(kf_p=[[0.0, 0.0, 1.0], [0.5, 0.5, 0.0], [0.0, 0.1, 1.0]], lkf=[[4.0, 3.2, 5.2]]), holes=(1,))
+        for name, (c, slots) in long_keyframe_cases().items():
+            add(name, c, slots=slots)
         return out
     return cached("aftertrack_keyframe_cases", make)
 
 
-def gathered(world, tracker):
-    """The restated gather as a tracker of need_keyframe_cases (what run_reference and desc_of take)."""
-    g = AR.gather_keyframe_desc(world, tracker["T_cur_w"], tracker["n_valid"], tracker["cur_point"], tracker["kf"], tracker["local_kf"])
+def gathered(world, tracker, gather=AR.gather_keyframe_desc):
+    """The restated gather (or a deliberately wrong one, for the non-vacuity checks) as a tracker of need_keyframe_cases (what
+    run_reference and desc_of take)."""
+    g = gather(world, tracker["T_cur_w"], tracker["n_valid"], tracker["cur_point"], tracker["kf"], tracker["local_kf"])
     return dict(cam=tracker["cam"], T_cur=g["T_cur_w"].reshape(3, 4), T_kf=g["T_kf_w"].reshape(3, 4), n_valid=g["n_valid"], cur_p=g["cur_p_world"], cur_bad=g["cur_bad"],
                 kf_p=g["kf_p_world"], kf_bad=g["kf_bad"], lkf=g["local_kf_centre"], params=tracker["params"])
 

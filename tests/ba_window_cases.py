@@ -1,11 +1,19 @@
-"""The worlds of libdsdtm_amd_mapping.so (include/dsdtm_amd_mapping.h), shared by the CPU and the GPU half of its tests: small maps built
-from the objects of tests/track_map_cases.py (at most 24 keyframes of at most 48 slots, except the limit cases), one case per rule edge.
+"""The worlds of libdsdtm_amd_mapping.so (include/dsdtm_amd_mapping.h), shared by the CPU and the GPU half of its tests. Two lists:
+all_cases() — small maps built from the objects of tests/track_map_cases.py (at most 24 keyframes of at most 48 slots, except the
+limit cases), one case per rule edge — and size_cases() — maps sized past the kernels' loop boundaries: keyframes of up to 4096 slots,
+up to 257 keyframes, windows of up to 700 entries, 76 keyframes and about 1000 observations, and point indices chosen by the kernels'
+hashes so that the two open-addressing tables chain, wrap and miss; one case per boundary, named for it. Every world is generated from
+a seed in the process. A size world is built from objects where sequential point indices do, and as plain arrays (Arrays, `objects`
+holds (None, None)) where the indices are chosen.
 A case is a dict: name, worlds (track_map_restatement's; `objects` holds the (kfs, mps) they came from), and what is asked of them:
     cov       [(world, kf, capacity or None)]                           dsdtm_mapping_covisibility
     windows   [(world, kf, cov_kf, origin_kf, kcap, pcap, ocap)]        dsdtm_mapping_ba_window (a capacity of None: room for all)
     outliers  {window: [(map point, map keyframe)]} or None             dsdtm_mapping_ba_commit with hand-set flags (None: no commit)
     overlap   (first, second) when the commit must be refused
+    room      the device capacities that stand for "room for all"; bad_capacity of the commit (None: room for all)
 expected(case) is the restatement's answer, computed once per session and never changed. Test infrastructure only."""
+from collections import Counter
+
 import numpy as np
 
 from dsdtm_amd import ba_window_restatement as BR
@@ -43,9 +51,9 @@ class World(Builder):
         return world_of(self.kfs, self.mps)
 
 
-def case(name, builders, cov=(), windows=(), outliers=None, overlap=None):
+def case(name, builders, cov=(), windows=(), outliers=None, overlap=None, room=ROOM, bad_capacity=None):
     return dict(name=name, worlds=[b.world() for b in builders], objects=[(b.kfs, b.mps) for b in builders], cov=list(cov), windows=list(windows),
-                outliers=outliers, overlap=overlap)
+                outliers=outliers, overlap=overlap, room=room, bad_capacity=bad_capacity)
 
 
 # ---- covisibility -----------------------------------------------------------------------------------------------------------------
@@ -228,6 +236,362 @@ def chain_property(win, outlier, commit):
     return int(np.count_nonzero(outlier)), commit["n_bad"], len(hit - set(commit["bad_points"]))
 
 
+# ---- size worlds: past one wavefront (64), one workgroup (256), 64 keyframes per workgroup, and the ends of the two hash tables ---------
+
+BIG_ROOM = dict(kcap=80, pcap=1024, ocap=4096)
+MULTIPLIER = 2654435761
+
+
+# The two hashes of csrc/mapping.hip, restated: cov_home is mp_hash13 (the covisibility table in LDS, 8192 cells), win_home is mp_hash
+# (the first-occurrence table of a window, 2^bits cells). The worlds below choose point indices by them, and the CPU property checks
+# model the tables with them: if a kernel's hash ever stops matching its restatement here, those checks cannot notice — the worlds
+# would still be answered correctly, but no longer chain, wrap or miss where their names say.
+def cov_home(p):
+    return ((p * MULTIPLIER) % 2 ** 32) >> 19
+
+
+def win_home(p, bits):
+    return ((p * MULTIPLIER) % 2 ** 32) >> (32 - bits)
+
+
+def table_bits(E):
+    """T_bits of a window with E entries: the smallest number of bits, from 4 up, with 2^bits >= 2E."""
+    bits = 4
+    while (1 << bits) < 2 * E:
+        bits += 1
+    return bits
+
+
+def probe_table(points, home, size):
+    """The model of either table: {cell: point} after the distinct points were inserted by linear probing. WHICH cells are taken does
+    not depend on the order of insertion (so it is what the device's table holds too); which point sits in which cell of a chain does."""
+    cells = {}
+    for p in points:
+        if p in cells.values():
+            continue
+        h = home(p)
+        while h in cells:
+            h = (h + 1) % size
+        cells[h] = p
+    return cells
+
+
+def probe_find(cells, home, size, p):
+    """(the cell of p or -1, the cells looked at): a probe ends at p or at an empty cell."""
+    h, walk = home(p), []
+    while h in cells:
+        walk.append(h)
+        if cells[h] == p:
+            return h, walk
+        h = (h + 1) % size
+    return -1, walk + [h]
+
+
+def cov_listed(world, kf):
+    """The points of keyframe kf's slots that the covisibility table holds (set, not bad), in slot order, repeated as listed."""
+    return [int(p) for p in world["slots"][kf] if p >= 0 and not world["bad"][p]]
+
+
+def cov_weights(world, kf):
+    """{keyframe: weight} of UpdateConnection, counted slot by slot (no set, no table): the property checks' own count."""
+    mult, out = Counter(cov_listed(world, kf)), {}
+    for k, (slots, obs) in enumerate(zip(world["slots"], world["observes"])):
+        w = sum(int(mult.get(int(p), 0)) for p, o in zip(slots, obs) if o and p >= 0)
+        if k != kf and w:
+            out[k] = w
+    return out
+
+
+def entries(world, kf, cov):
+    """The entries of a window in order: the slots of tKFrame, then of each covisible keyframe (a point index or -1)."""
+    return [int(p) for k in [kf] + list(cov) for p in world["slots"][k]]
+
+
+class Arrays:
+    """A world as plain arrays, for the cases whose point indices are chosen: keyframes are lists of point indices (-1: a NULL slot)."""
+    kfs = mps = None
+
+    def __init__(self, seed, n_points):
+        self.seed, self.rng, self.P, self.slots, self.observes, self.bad = seed, np.random.default_rng(seed), n_points, [], [], np.zeros(n_points, np.uint8)
+
+    def kf(self, slots, observes=None):
+        """A keyframe; every set slot observes unless `observes` says otherwise. Returns its index."""
+        s = np.array(slots, np.int32).reshape(-1)
+        self.slots.append(s)
+        self.observes.append((s >= 0).astype(np.uint8) if observes is None else np.array(observes, np.uint8).reshape(-1) & (s >= 0))
+        return len(self.slots) - 1
+
+    def world(self):
+        K = len(self.slots)
+        T = np.tile(np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float64), (K, 1))
+        T[:, 3] = -0.125 * np.arange(K)
+        draw = lambda k, column: np.random.default_rng([self.seed, k, column])       # (a slot's features depend on (keyframe, slot) alone: siblings agree)
+        bearing = []
+        for k, s in enumerate(self.slots):
+            n = draw(k, 0).normal(size=(len(s), 3))
+            bearing.append(n / np.linalg.norm(n, axis=1, keepdims=True))
+        return dict(p_world=draw(len(self.slots), 3).uniform(-2.0, 2.0, (self.P, 3)), bad=self.bad.copy(), found=np.ones(self.P, np.int32), T_kf_w=T,
+                    slots=[s.copy() for s in self.slots], observes=[o.copy() for o in self.observes],
+                    px=[draw(k, 1).uniform(1, 400, (len(s), 2)).astype(np.float32) for k, s in enumerate(self.slots)],
+                    level=[draw(k, 2).integers(0, 4, len(s)).astype(np.int32) for k, s in enumerate(self.slots)], bearing=bearing)
+
+
+def cov_wide_keyframes():
+    """kf 0 has 300 slots (two trips of the 256-thread fill loop) and lists one point in both trips; keyframes 1, 2, 3 have 64, 65 and
+    130 slots, each with its LAST slot observing a point of kf 0 (slots 255, 256 and 299 of it). Weights: 15, 16 and 20."""
+    b = World(61)
+    k = [b.kf(n) for n in (300, 64, 65, 130, 40)]
+    mine = [b.new_point(k[0], s) for s in range(270)]                                # by slot of keyframe 0
+    b.link(k[0], 270, mine[10], observe=False)                                       # slots 10 and 270: it counts twice
+    mine += [mine[10]] + [b.new_point(k[0], s) for s in range(271, 300)]
+
+    def observe(kf, pairs):
+        for s, s0 in pairs:
+            b.link(kf, s, mine[s0])
+    observe(k[1], [(s, 20 + s) for s in range(14)] + [(63, 255)])
+    observe(k[2], [(s, 40 + s) for s in range(15)] + [(64, 256)])
+    observe(k[3], [(60 + s, 100 + s) for s in range(11)] + [(5, 10), (129, 299)] + [(120 + s, 280 + s) for s in range(6)])
+    for kf in k[1:]:
+        for s in range(20, 30):
+            b.new_point(kf, s)
+    return case("cov_wide_keyframes", [b], cov=[(0, 0, 8), (0, 3, 8)])
+
+
+def cov_K_world(K):
+    """K keyframes around two hubs, keyframe 0 and keyframe K - 1. Against hub 0, keyframes 5, K - 57, K - 1 and K // 2 + 1 weigh 16, 17,
+    17 and 18, every other one 1..3; against hub K - 1, keyframes 3, 0 and K - 2 weigh 16, 17 and 20. With K = 257 keyframe 1 is a
+    third hub with nothing above 15: keyframes 130 and 256 both weigh 11, keyframe 2 weighs 3."""
+    b = World(60 + K)
+    k = [b.kf(3 * K + 100)] + [b.kf(48) for _ in range(K - 2)] + [b.kf(3 * K + 100)]
+    over = {5: 16, K - 57: 17, K - 1: 17, K // 2 + 1: 18}
+    for i in range(1, K):
+        b.share(k[0], k[i], over.get(i, 1 + i % 3))
+    over = {3: 16, K - 2: 20}
+    for i in range(1, K - 1):
+        b.share(k[K - 1], k[i], over.get(i, 1 + i % 2))
+    if K == 257:
+        b.share(k[1], k[256], 9)                                                     # + the 2 it shares with that hub already
+        b.share(k[1], k[130], 11)
+        b.share(k[1], k[2], 3)
+    return b
+
+
+def cov_K(K):
+    pairs = [(0, 0, 8), (0, 0, 3), (0, K - 1, 8), (0, K - 1, 2)]
+    if K == 257:                                                                     # the fallback: room for the one it names, and none
+        pairs += [(0, 1, 8), (0, 1, 0)]
+    worlds = [cov_K_world(K)]
+    if K == 65:                                                                      # a 64-keyframe map in the same call: its second workgroup has no keyframe
+        worlds.append(cov_K_world(64))
+        pairs += [(1, 0, 8), (1, 63, 8)]
+    return case(f"cov_K_{K}", worlds, cov=pairs)
+
+
+def cov_table_chains():
+    """24 000 points, indices chosen by cov_home. kf 0 lists four good points of one home cell H (a chain H .. H + 3), a bad point whose
+    home is H + 1 (inside the chain: not inserted), both points whose home is cell 8191 and one whose home is cell 0 (a chain 8191, 0,
+    1), and twelve points elsewhere. Keyframe 1 observes the chain at H, the bad point, a fifth point of home H that is NOT listed
+    (its probe walks the chain to the empty cell H + 4), one point of the wrapping chain and the twelve: 4 + 1 + 12 = 17. Keyframe 2
+    observes the wrapping chain and an unlisted point of home 0 (its probe ends at the empty cell 2): 3."""
+    P = 24000
+    homes = {}
+    for p in range(P):
+        homes.setdefault(cov_home(p), []).append(p)
+    H = [h for h in sorted(homes) if 100 < h < 8000 and len(homes[h]) >= 5 and homes.get(h + 1)][0]
+    chain, miss, bad = homes[H][:4], homes[H][4], homes[H + 1][0]
+    wrap = homes[8191][:2] + homes[0][:1]
+    miss_wrap = homes[0][1]
+    taken = set(range(H - 1, H + 6)) | {8190, 8191, 0, 1, 2, 3}
+    filler = [homes[h][0] for h in sorted(homes) if h not in taken and all(abs(h - t) > 8 for t in (H, 0, 8191))][5:5 + 12 * 40:40]
+    a = Arrays(62, P)
+    a.bad[bad] = 1
+    a.kf([chain[0], filler[0], chain[1], bad, wrap[2], chain[2]] + filler[1:7] + [wrap[0], chain[3], wrap[1]] + filler[7:])
+    a.kf(chain[::-1] + [bad, miss, wrap[1]] + filler)
+    a.kf([wrap[0], miss_wrap, wrap[1], wrap[2]])
+    c = case("cov_table_chains", [a], cov=[(0, 0, 8)])
+    c["marks"] = dict(H=H, chain=chain, miss=miss, bad=bad, wrap=wrap, miss_wrap=miss_wrap)
+    return c
+
+
+def cov_table_full():
+    """World 0: kf 0 has 4096 slots listing 4096 distinct good points (the table at load 0.5; indices drawn from 30 000, so that home
+    cells collide); keyframe 1 observes all of them, keyframe 2 observes 4096 points kf 0 does not list. World 1: all 4096 slots of
+    kf 0 list ONE point (the first slot observes it), keyframe 1 observes it once: weight 4096, 13 bits of the 16-bit count."""
+    a = Arrays(63, 30000)
+    pick = a.rng.permutation(30000)[:8192]
+    a.kf(pick[:4096])
+    a.kf(a.rng.permutation(pick[:4096]))
+    a.kf(pick[4096:])
+    b = Arrays(64, 16)
+    b.kf([7] * 4096, [1] + [0] * 4095)
+    b.kf([3, 7, -1])
+    return case("cov_table_full", [a, b], cov=[(0, 0, 4), (1, 0, 4)])
+
+
+WINDOW_E = {256: dict(sizes=(40, 60, 56, 50, 50), bad_at=255, null_at=254, twice=None),
+            257: dict(sizes=(40, 60, 56, 50, 51), bad_at=100, null_at=255, twice=None),
+            700: dict(sizes=(100, 156, 144, 150, 150), bad_at=255, null_at=256, twice=(5, 570))}
+
+
+def window_E_world(E):
+    """Six outside keyframes (0..5), then 1 + 4 local ones whose slot counts sum to E: tKFrame is keyframe 6 (its slots are the entries
+    from 0 on), 7..10 are covisible. An entry lists a new point, except: entry `null_at` is a NULL slot, entry `bad_at` lists a bad
+    point, entry twice[1] lists the point of entry twice[0] again, and every entry e with e % 7 == 3 relists a point of an earlier local
+    keyframe (where there is one that this keyframe does not hold yet). Every third window point has an outside observer, every ninth two. Returns
+    (builder, window spec)."""
+    spec = WINDOW_E[E]
+    b = World(70 + E)
+    fixed = [b.kf(80) for _ in range(6)]
+    local = [b.kf(n) for n in spec["sizes"]]
+    e, at_entry, earlier, window_points = 0, {}, [], []
+    for kf in local:
+        here = []
+        for _ in range(len(kf.mvMapPoints)):
+            old = None
+            if spec["twice"] and e == spec["twice"][1]:
+                old = at_entry[spec["twice"][0]]
+            elif e % 7 == 3 and earlier and e not in (spec["null_at"], spec["bad_at"]):
+                old = earlier[(5 * e) % len(earlier)]
+                old = None if old in kf.mvMapPoints else old
+            if e == spec["null_at"]:
+                b.slot(kf)
+            elif e == spec["bad_at"]:
+                b.point(kf).SetBadFlag()
+            elif old is not None:
+                b.see(kf, old)
+            else:
+                at_entry[e] = b.point(kf)
+                here.append(at_entry[e])
+                window_points.append(at_entry[e])
+            e += 1
+        earlier += here
+    assert e == E
+    for j, mp in enumerate(window_points[::3]):
+        b.see(fixed[j % 6], mp)
+    for j, mp in enumerate(window_points[::9]):                                      # (a second one for every ninth: never the same keyframe)
+        b.see(fixed[(j + 3) % 6], mp)
+    return b, (0, 6, [7, 8, 9, 10], -1, None, None, None)
+
+
+def window_E(E):
+    b, spec = window_E_world(E)
+    return case(f"window_E_{E}", [b], windows=[spec], room=BIG_ROOM)
+
+
+LONG_A, LONG_B = 7, 30
+
+
+def window_long_segments():
+    """60 outside keyframes (0..59), tKFrame 60 with 121 slots, 15 covisible keyframes of 9 slots. Window point 120 (the last slot of
+    tKFrame) is observed by all 76 keyframes. Outside keyframe LONG_A has 130 slots and observes that point alone, at slot 129; LONG_B
+    observes window point 101 at slot 3 and window point 11 at slot 70 (its place among the fixed keyframes is 11's, found by the
+    wavefront's second trip); every other outside keyframe i observes window point 2 * (7 i mod 59) and point 120."""
+    b = World(81)
+    fixed = [b.kf(130 if i == LONG_A else 80 if i == LONG_B else 8) for i in range(60)]
+    local = [b.kf(121)] + [b.kf(9) for _ in range(15)]
+    pts = [b.point(local[0]) for _ in range(121)]
+    for kf in local[1:]:
+        for _ in range(8):
+            b.point(kf)
+        b.see(kf, pts[120])
+    for i, f in enumerate(fixed):
+        if i == LONG_A:
+            b.link(f, 129, pts[120])
+        elif i == LONG_B:
+            b.link(f, 3, pts[101])
+            b.link(f, 70, pts[11])
+            b.link(f, 71, pts[120])
+        else:
+            b.see(f, pts[2 * ((7 * i) % 59)])
+            b.see(f, pts[120])
+    return case("window_long_segments", [b], windows=[(0, 60, list(range(61, 76)), -1, None, None, None)])
+
+
+def window_table_chains():
+    """Chosen indices, two sibling worlds with the same points. World 0: tKFrame 0 has 5 slots, the covisible keyframe 1 has 3: E = 8,
+    T_bits = 4, 16 cells. Five of the seven window points have home cell 14 (the chain 14, 15, 0, 1, 2); point `twice` is listed by
+    both keyframes; the outside keyframe 2 observes `miss`, not a window point, whose home is cell 15 (its probe walks 15, 0, 1, 2 and
+    ends at the empty cell 3), and two window points. World 1: keyframe 1 has a fourth, NULL slot: E = 9, T_bits = 5, 32 cells — the same
+    window out of another table."""
+    P = 128
+    chain = [p for p in range(P) if win_home(p, 4) == 14][:5]
+    a, c = [[p for p in range(P) if win_home(p, 4) == h][0] for h in (6, 9)]
+    miss = [p for p in range(P) if win_home(p, 4) == 15][0]
+    twice = chain[1]
+    worlds = []
+    for extra in ([], [-1]):
+        w = Arrays(65, P)
+        w.kf(chain[:3] + [a, chain[3]])
+        w.kf([chain[4], c, twice] + extra)
+        w.kf([miss, chain[2], a, -1])
+        worlds.append(w)
+    out = case("window_table_chains", worlds, windows=[(0, 0, [1], -1, None, None, None), (1, 0, [1], -1, None, None, None)])
+    out["marks"] = dict(chain=chain, others=[a, c], miss=miss, twice=twice)
+    return out
+
+
+def window_mixed_call():
+    """One call of three very different windows: window_E_700's, a 5-entry window on a 6-keyframe map, and a window with 64 fixed
+    keyframes on a 66-keyframe map (tKFrame 64: the second workgroup of the scan kernels holds the local keyframes)."""
+    big, spec = window_E_world(700)
+    tiny = World(82)
+    k = [tiny.kf(6) for _ in range(4)] + [tiny.kf(2), tiny.kf(3)]
+    tiny.share(k[4], k[5], 1)
+    tiny.share(k[4], k[0], 1)
+    tiny.share(k[5], k[1], 2)
+    for kf in k[:4]:
+        tiny.point(kf)
+    wide = World(83)
+    fixed = [wide.kf(2) for _ in range(64)]
+    first, second = wide.kf(70), wide.kf(10)
+    for f in fixed:
+        wide.see(f, wide.point(first))
+    wide.share(first, second, 5)
+    return case("window_mixed_call", [big, tiny, wide], windows=[spec, (1, 4, [5], -1, None, None, None), (2, 64, [65], -1, None, None, None)], room=BIG_ROOM)
+
+
+def commit_many_points(short):
+    """window_E_700's window: every observation of every even window point, and of window points 255 and 256, is an outlier (they all go
+    bad: more than 256 of them, in every 256-chunk of the window) — except the first window point from 512 on with three observations or
+    more, which gets one outlier and stays good. bad_capacity: room for all, or short by one."""
+    b, spec = window_E_world(700)
+    win = BR.ba_window(b.world(), 6, [7, 8, 9, 10], -1)
+    by_point = {}
+    for j, i in enumerate(win["obs_point"]):
+        by_point.setdefault(int(i), []).append((int(win["point_index"][i]), int(win["obs_slot"][j]) >> 32))
+    stays = [i for i in range(512, win["n_points"]) if len(by_point[i]) >= 3][0]
+    goes_bad = [i for i in range(win["n_points"]) if (i % 2 == 0 or i in (255, 256)) and i != stays]
+    pairs = [pair for i in goes_bad for pair in by_point[i]] + by_point[stays][1:2]
+    c = case("commit_many_points" + ("_bad_capacity_short_by_one" if short else ""), [b], windows=[spec], outliers={0: pairs}, room=BIG_ROOM,
+             bad_capacity=len(goes_bad) - int(short))
+    c["marks"] = dict(goes_bad=goes_bad, stays=stays)
+    return c
+
+
+def commit_overlap_beyond_256():
+    """Two usable windows on one map, tKFrame 1 alone and tKFrame 2 alone, that share no keyframe and exactly one map point: listed by
+    both keyframes and observed by nobody (an observer would be a fixed keyframe of both windows), at place 280 of the first window's
+    points and 270 of the second's — the second workgroup of the claim kernels."""
+    b = World(84)
+    k = [b.kf(4), b.kf(300), b.kf(300)]
+    b.point(k[0])
+    for _ in range(280):
+        b.point(k[1])
+    for _ in range(270):
+        b.point(k[2])
+    shared = b.point(k[1], observe=False)
+    b.see(k[2], shared, observe=False)
+    c = case("commit_overlap_beyond_256", [b], windows=[(0, 1, [], -1, None, None, None), (0, 2, [], -1, None, None, None)], outliers={0: [], 1: []}, overlap=(0, 1))
+    c["marks"] = dict(shared=shared.mlID)
+    return c
+
+
+def size_cases():
+    return cached("ba_window_size", lambda: [cov_wide_keyframes(), cov_K(64), cov_K(65), cov_K(257), cov_table_chains(), cov_table_full(),
+                                             window_E(256), window_E(257), window_E(700), window_long_segments(), window_table_chains(), window_mixed_call(),
+                                             commit_many_points(False), commit_many_points(True), commit_overlap_beyond_256()])
+
+
 def all_cases():
     return cached("ba_window_all", lambda: [cov_threshold(), cov_fallback_tie(), cov_nothing_shared(), cov_listed_twice_unobserved_and_bad(), cov_equal_weights(),
                                             window_basic(), window_origin(), window_short_capacities(), window_two_on_one_map_two_maps(), window_free_limit(),
@@ -235,7 +599,7 @@ def all_cases():
 
 
 def by_name(name):
-    return [c for c in all_cases() if c["name"] == name][0]
+    return [c for c in all_cases() + size_cases() if c["name"] == name][0]
 
 
 def flags_of(window, pairs):
@@ -259,7 +623,7 @@ def expected(c):
                     e["commits"].append(None)
                     continue
                 m = c["windows"][i][0]
-                worlds[m], r = BR.ba_commit(worlds[m], win, win["T_c2w"], win["points"], e["flags"][i])
+                worlds[m], r = BR.ba_commit(worlds[m], win, win["T_c2w"], win["points"], e["flags"][i], c["bad_capacity"])
                 e["commits"].append(r)
             e["worlds_after"] = worlds
         return e

@@ -194,6 +194,83 @@ def test_gathered_keyframe_lists_agree_and_decide_as_the_tracker_they_were_made_
             AR.gather_keyframe_desc(world, q["T_cur_w"], q["n_valid"], q["cur_point"], q["kf"], q["local_kf"])
 
 
+def _round_lists(world, kf):
+    """The restated gather of each 256-slot round of keyframe kf alone: [(kf_p_world, kf_bad)]."""
+    out = []
+    for s0 in range(0, len(world["slots"][kf]), cases.ROUND):
+        one = dict(world, slots=[s[s0:s0 + cases.ROUND] if k == kf else s for k, s in enumerate(world["slots"])])
+        g = AR.gather_keyframe_desc(one, np.zeros(12), 0, [], kf, [])
+        out.append((g["kf_p_world"], g["kf_bad"]))
+    return out
+
+
+def gather_base_not_carried(world, T_cur_w, n_valid, cur_point, kf, local_kf):
+    """A deliberately WRONG gather: every round compacts from 0, so a round overwrites the front of the list the earlier rounds left
+    (the list is as long as the longest round's)."""
+    g = AR.gather_keyframe_desc(world, T_cur_w, n_valid, cur_point, kf, local_kf)
+    rounds = _round_lists(world, kf)
+    n = max([len(b) for _, b in rounds] + [0])
+    p, bad = np.zeros((n, 3)), np.zeros(n, np.uint8)
+    for rp, rb in rounds:
+        p[:len(rb)], bad[:len(rb)] = rp, rb
+    return dict(g, kf_p_world=p, kf_bad=bad)
+
+
+def gather_later_rounds_dropped(world, T_cur_w, n_valid, cur_point, kf, local_kf):
+    """A deliberately WRONG gather: the rounds after the first are dropped."""
+    g = AR.gather_keyframe_desc(world, T_cur_w, n_valid, cur_point, kf, local_kf)
+    rounds = _round_lists(world, kf)
+    return dict(g, kf_p_world=rounds[0][0], kf_bad=rounds[0][1]) if rounds else g
+
+
+def test_the_long_keyframes_verdicts_depend_on_the_later_rounds_of_the_gather():
+    """The gather is visible only through the verdict, and K2 stops after 31 samples: each long last keyframe is arranged so that a
+    gather that loses the running base, or the rounds after the first, gives OTHER reference verdict bytes — except kf_256_slots, which
+    has no second round (there all three agree). WHAT CANNOT DIFFER: on kf_600_slots_all_samples_from_round_three the base-not-carried
+    gather gives the SAME verdict as the faithful one, whatever it leaves behind the overwritten front: rounds one and two hold no good
+    point, so the first 31 good points of either list are round three's, in the same order. That world is held to the lost base by
+    its gathered list (which differs) and to the dropped rounds by its verdict; the two worlds with good points in front of the
+    later rounds show the lost base in the verdict."""
+    from tests import need_keyframe_cases as NK
+    by = {name: (world, t) for name, world, t in cases.keyframe_cases()}
+
+    def verdict(world, t, gather):
+        r = NK.run_reference(cases.gathered(world, t, gather))
+        return struct.pack("7i5d", *[r[k] for k in NK.INT_FIELDS + NK.FLOAT_FIELDS]), r
+    want_n_px = {"kf_256_slots": 31, "kf_257_slots_31st_sample_in_round_two": 31, "kf_600_slots_all_samples_from_round_three": 31, "kf_round_two_waves_1_and_3_only": 31}
+    for name in cases.long_keyframe_cases():
+        world, t = by[name]
+        good, r = verdict(world, t, AR.gather_keyframe_desc)
+        no_base, dropped = verdict(world, t, gather_base_not_carried)[0], verdict(world, t, gather_later_rounds_dropped)[0]
+        assert r["n_px"] == want_n_px[name] and r["undefined"] == 0, (name, r)
+        if name == "kf_256_slots":
+            assert no_base == good and dropped == good
+            continue
+        assert dropped != good, name
+        if name == "kf_600_slots_all_samples_from_round_three":
+            a, b = cases.gathered(world, t), cases.gathered(world, t, gather_base_not_carried)
+            assert no_base == good and (len(a["kf_bad"]) != len(b["kf_bad"]) or a["kf_p"].tobytes() != b["kf_p"].tobytes())
+        else:
+            assert no_base != good, name
+    # and what each world is named for
+    slots = {name: by[name][0]["slots"][0] for name in cases.long_keyframe_cases()}
+    bad = {name: by[name][0]["bad"] for name in slots}
+    good_slots = lambda name: [s for s, p in enumerate(slots[name]) if p >= 0 and not bad[name][p]]
+    assert len(slots["kf_256_slots"]) == 256 and (slots["kf_256_slots"] >= 0).all() and good_slots("kf_256_slots")[30] == 30
+    g = good_slots("kf_257_slots_31st_sample_in_round_two")
+    r = verdict(*by["kf_257_slots_31st_sample_in_round_two"], AR.gather_keyframe_desc)[1]
+    assert len(slots["kf_257_slots_31st_sample_in_round_two"]) == 257 and len(g) == 31 and g[30] == 256 and r["median_px"] == 128.0
+    assert sorted(r["px_dist"]) == [8.0] * 15 + [128.0] + [4096.0] * 15 and (slots["kf_257_slots_31st_sample_in_round_two"][:256] < 0).any()
+    assert int(bad["kf_257_slots_31st_sample_in_round_two"][slots["kf_257_slots_31st_sample_in_round_two"][:256][slots["kf_257_slots_31st_sample_in_round_two"][:256] >= 0]].sum()) == 30
+    s, g = slots["kf_600_slots_all_samples_from_round_three"], good_slots("kf_600_slots_all_samples_from_round_three")
+    assert len(s) == 600 and len(g) == 40 and min(g) >= 512 and (s[[255, 256, 511, 512]] == -1).all() and (s[[254, 257, 510]] >= 0).all()
+    assert len(set(verdict(*by["kf_600_slots_all_samples_from_round_three"], AR.gather_keyframe_desc)[1]["px_dist"])) == 31
+    s, g = slots["kf_round_two_waves_1_and_3_only"], good_slots("kf_round_two_waves_1_and_3_only")
+    in_round_two = np.flatnonzero(s[256:] >= 0)
+    assert len(s) == 512 and set((in_round_two // 64).tolist()) == {1, 3} and len(in_round_two) == 128 and 0 < int((s[:256] >= 0).sum()) < 256
+    assert [x for x in g[:31] if x < 256] == g[:10] and [x for x in g[:31] if 320 <= x < 384] == g[10:15] and min(g[15:31]) >= 448      # samples from both wavefronts
+
+
 def test_example_and_adapter_compile():
     """example_aftertrack.cpp uses Tracking::CommitTrackedFrameOnDevice of dsdtm_slam_host.hpp and track_commit_host: the compiler sees
     them here."""

@@ -16,7 +16,8 @@ from dsdtm_amd.optimizer import Optimizer
 from tests import ba_window_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WINDOWED = [c for c in cases.all_cases() if c["windows"]]
+EVERY = cases.all_cases() + cases.size_cases()
+WINDOWED = [c for c in EVERY if c["windows"] and c["objects"][0][0] is not None]      # (a world of plain arrays has no objects to walk)
 
 
 @pytest.mark.parametrize("c", WINDOWED, ids=lambda c: c["name"])
@@ -55,7 +56,7 @@ def test_restated_commit_equals_the_objects_bookkeeping():
     """The outlier pass on the objects — MapPoint::Erase_Observation, then KeyFrame::Erase_MapPointMatch, with SetBadFlag as
     src/MapPoint.cpp:91-109 has it (mapping.MapPoint.SetBadFlag only sets the flag, so the clearing of the observers is done here, by
     hand, from the source) — against ba_commit on every commit case."""
-    for c in [c for c in cases.all_cases() if c["outliers"] is not None and not c["overlap"]]:
+    for c in [c for c in EVERY if c["outliers"] is not None and not c["overlap"]]:
         e = cases.expected(c)
         kfs, mps = copy.deepcopy(c["objects"][0])
         win = e["windows"][0]
@@ -74,7 +75,10 @@ def test_restated_commit_equals_the_objects_bookkeeping():
             kf.Erase_MapPointMatch(mp)
         after = cases.world_of(kfs, mps)
         cases.same_world(after, e["worlds_after"][0], c["name"])
-        assert n_out == e["commits"][0]["n_outliers"] and [p for p, mp in enumerate(mps) if mp.IsBad()] == e["commits"][0]["bad_points"]
+        was_bad = {p for p, mp in enumerate(c["objects"][0][1]) if mp.IsBad()}
+        went_bad = [p for p, mp in enumerate(mps) if mp.IsBad() and p not in was_bad]      # (bad before the commit: a size world's bad entry)
+        full = e["commits"][0]["bad_points"] if c["bad_capacity"] is None else BR.ba_commit(c["worlds"][0], win, win["T_c2w"], win["points"], e["flags"][0])[1]["bad_points"]
+        assert n_out == e["commits"][0]["n_outliers"] and went_bad == full and len(full) == e["commits"][0]["n_bad"]
 
 
 def test_the_cases_reach_what_they_are_named_for():
@@ -108,6 +112,125 @@ def test_the_cases_reach_what_they_are_named_for():
     assert p in after["slots"][k] and p not in after["slots"][3] and after["bad"][p] == 1 and not after["observes"][k][list(after["slots"][k]).index(p)]
 
 
+def test_the_size_cases_cross_what_they_are_named_for():
+    """Every size world against the boundary its name claims, on the restatement's answer and on the Python model of the two tables
+    (cases.probe_table with the restated hashes): a size world that stops crossing its boundary fails HERE, not vacuously on the GPU."""
+    size = {c["name"]: c for c in cases.size_cases()}
+    by = {n: cases.expected(c) for n, c in size.items()}
+    W = lambda name, m=0: size[name]["worlds"][m]
+    n_slots = lambda name, m=0: [len(s) for s in W(name, m)["slots"]]
+    # -- covisibility
+    w = W("cov_wide_keyframes")
+    assert n_slots("cov_wide_keyframes")[:4] == [300, 64, 65, 130] and w["slots"][0][10] == w["slots"][0][270] >= 0
+    for k, s0 in ((1, 255), (2, 256), (3, 299)):                              # the last slot observes what kf 0 lists at slot 255 / 256 / 299
+        assert w["observes"][k][-1] == 1 and w["slots"][k][-1] == w["slots"][0][s0]
+    assert w["slots"][0][10] in w["slots"][3] and np.flatnonzero(np.isin(w["slots"][3], w["slots"][0]) & (w["observes"][3] == 1)).max() == 129
+    assert np.count_nonzero(np.isin(w["slots"][3][64:128], w["slots"][0])) > 0 and np.count_nonzero(np.isin(w["slots"][3][:64], w["slots"][0])) > 0
+    assert cases.cov_weights(w, 0) == {1: 15, 2: 16, 3: 20} and by["cov_wide_keyframes"]["cov"][0] == dict(n_cov=2, n_connected=3, overflow=0, cov_kf=[2, 3], cov_weight=[16, 20])
+    for K in (64, 65, 257):
+        c, e = size[f"cov_K_{K}"], by[f"cov_K_{K}"]["cov"]
+        assert len(c["worlds"][0]["slots"]) == K and [q[1] for q in c["cov"][:4]] == [0, 0, K - 1, K - 1]
+        assert e[0]["cov_kf"] == [5, K - 57, K - 1, K // 2 + 1] and e[0]["cov_weight"] == [16, 17, 17, 18] and e[0]["n_connected"] == K - 1 and e[0]["overflow"] == 0
+        assert e[1]["overflow"] == 1 and e[1]["cov_kf"] == e[0]["cov_kf"][:3] and e[2]["cov_kf"] == [3, 0, K - 2] and e[3]["overflow"] == 1 and e[3]["cov_kf"] == [3, 0]
+    assert len(W("cov_K_65", 1)["slots"]) == 64 and [q[0] for q in size["cov_K_65"]["cov"][4:]] == [1, 1]
+    e, wt = by["cov_K_257"]["cov"], cases.cov_weights(W("cov_K_257"), 1)
+    assert 256 in e[0]["cov_kf"] and e[0]["cov_kf"].index(256) == 2                 # above the threshold, at its rank
+    assert max(wt.values()) == 11 <= BR.COV_THRESHOLD and sorted(k for k in wt if wt[k] == 11) == [130, 256]      # the tie: 130 < 256 wins
+    assert e[4] == dict(n_cov=1, n_connected=4, overflow=0, cov_kf=[130], cov_weight=[11]) and e[5]["overflow"] == 1 and e[5]["cov_kf"] == []
+    c, w = size["cov_table_chains"], W("cov_table_chains")
+    m = c["marks"]
+    assert len(w["bad"]) == 24000
+    table = cases.probe_table(cases.cov_listed(w, 0), cases.cov_home, 8192)
+    H = m["H"]
+    assert [cases.cov_home(p) for p in m["chain"]] == [H] * 4 and sorted(table[H + i] for i in range(4)) == sorted(m["chain"]) and H + 4 not in table
+    assert cases.cov_home(m["miss"]) == H and m["miss"] not in w["slots"][0] and m["miss"] in w["slots"][1]
+    assert cases.probe_find(table, cases.cov_home, 8192, m["miss"]) == (-1, [H, H + 1, H + 2, H + 3, H + 4])      # walks the chain, ends at an empty cell
+    assert H <= cases.cov_home(m["bad"]) <= H + 3 and w["bad"][m["bad"]] == 1 and m["bad"] in w["slots"][0] and m["bad"] in w["slots"][1] and m["bad"] not in table.values()
+    assert [cases.cov_home(p) for p in m["wrap"]] == [8191, 8191, 0] and {8191, 0, 1} <= set(table) and 2 not in table and 8190 not in table
+    assert sorted(table[h] for h in (8191, 0, 1)) == sorted(m["wrap"]) and cases.probe_find(table, cases.cov_home, 8192, m["wrap"][2])[1][-1] >= 0
+    assert max(len(cases.probe_find(table, cases.cov_home, 8192, p)[1]) for p in m["wrap"]) >= 2      # some point of the wrapping chain sits past its home cell
+    assert cases.cov_home(m["miss_wrap"]) == 0 and cases.probe_find(table, cases.cov_home, 8192, m["miss_wrap"]) == (-1, [0, 1, 2]) and m["miss_wrap"] in w["slots"][2]
+    assert cases.cov_weights(w, 0) == {1: 17, 2: 3} and by["cov_table_chains"]["cov"][0]["cov_kf"] == [1] and by["cov_table_chains"]["cov"][0]["cov_weight"] == [17]
+    w = W("cov_table_full")
+    listed = cases.cov_listed(w, 0)
+    table = cases.probe_table(listed, cases.cov_home, 8192)
+    assert len(listed) == len(set(listed)) == 4096 == len(table) and 2 * len(table) == 8192          # load 0.5
+    assert max(len(cases.probe_find(table, cases.cov_home, 8192, p)[1]) for p in listed) >= 3         # and real chains in it
+    assert set(w["slots"][1].tolist()) == set(listed) and not set(w["slots"][2].tolist()) & set(listed) and len(set(w["slots"][2].tolist())) == 4096
+    assert cases.cov_weights(w, 0) == {1: 4096} and by["cov_table_full"]["cov"][0] == dict(n_cov=1, n_connected=1, overflow=0, cov_kf=[1], cov_weight=[4096])
+    w = W("cov_table_full", 1)
+    assert len(set(w["slots"][0].tolist())) == 1 and len(w["slots"][0]) == 4096 and int(w["observes"][1][w["slots"][1] == 7].sum()) == 1
+    assert cases.cov_weights(w, 0) == {1: 4096} and by["cov_table_full"]["cov"][1]["cov_weight"] == [4096] and 4096 >= 1 << 12      # the 13th bit of the half word
+    # -- window
+    for E, bits in ((256, 9), (257, 10), (700, 11)):
+        c, win = size[f"window_E_{E}"], by[f"window_E_{E}"]["windows"][0]
+        w, (_, kf, cov, _, _, _, _) = c["worlds"][0], c["windows"][0]
+        ent = cases.entries(w, kf, cov)
+        good = [p for p in ent if p >= 0 and not w["bad"][p]]
+        first = {e for e, p in enumerate(ent) if p >= 0 and not w["bad"][p] and p not in ent[:e]}
+        assert len(cov) == 4 and len(ent) == E and cases.table_bits(E) == bits and win["usable"] == 1
+        assert win["n_points"] == len(first) == len(set(good)) and win["n_obs"] > 256 and win["point_index"].tolist() == [ent[e] for e in sorted(first)]
+        spec = cases.WINDOW_E[E]
+        assert ent[spec["null_at"]] == -1 and w["bad"][ent[spec["bad_at"]]] == 1 and {spec["null_at"], spec["bad_at"]} & {255, 256}
+        assert len(good) > len(first)                                               # points listed by several local keyframes
+    assert 256 in {e for e, p in enumerate(cases.entries(W("window_E_257"), 6, [7, 8, 9, 10])) if p >= 0 and p not in cases.entries(W("window_E_257"), 6, [7, 8, 9, 10])[:e]}
+    assert (cases.WINDOW_E[256]["bad_at"], cases.WINDOW_E[257]["null_at"], cases.WINDOW_E[700]["bad_at"], cases.WINDOW_E[700]["null_at"]) == (255, 255, 255, 256)
+    ent, win = cases.entries(W("window_E_700"), 6, [7, 8, 9, 10]), by["window_E_700"]["windows"][0]
+    first = [e for e, p in enumerate(ent) if p >= 0 and not W("window_E_700")["bad"][p] and p not in ent[:e]]
+    assert all(any(lo <= e < lo + 256 for e in first) for lo in (0, 256, 512)) and win["n_points"] > 512 and win["n_points"] <= 800 and win["n_obs"] <= 3000
+    assert ent[5] == ent[570] >= 0 and win["point_index"].tolist().count(ent[5]) == 1 and win["point_index"].tolist().index(ent[5]) == first.index(5)
+    c, win = size["window_long_segments"], by["window_long_segments"]["windows"][0]
+    w = c["worlds"][0]
+    assert (win["n_local"], win["n_fixed"], win["usable"]) == (16, 60, 1) and c["windows"][0][3] == -1
+    seg = np.bincount(win["obs_point"], minlength=win["n_points"])
+    X = int(win["point_index"][120])
+    assert seg.max() == seg[120] == 76 and sorted(int(s) >> 32 for s in win["obs_slot"][win["obs_point"] == 120]) == list(range(76))
+    A, B = cases.LONG_A, cases.LONG_B
+    in_window = lambda k: [(s, win["point_index"].tolist().index(int(p))) for s, (p, o) in enumerate(zip(w["slots"][k], w["observes"][k])) if o and p in win["point_index"]]
+    assert len(w["slots"][A]) == 130 and in_window(A) == [(129, 120)] and w["slots"][A][129] == X
+    assert in_window(B) == [(3, 101), (70, 11), (71, 120)]
+    fixed = win["kf_index"][16:].tolist()
+    keys = {k: min(i for _, i in in_window(k)) for k in fixed}
+    assert fixed == sorted(fixed, key=lambda k: (keys[k], k)) and fixed[-1] == A and keys[B] == 11
+    between = [k for k in fixed if 11 < keys[k] < 101]
+    assert between and fixed.index(B) < fixed.index(between[0])                     # (with slot 70 lost, B would stand behind these)
+    c, e = size["window_table_chains"], by["window_table_chains"]["windows"]
+    m = c["marks"]
+    for world, E, bits in ((0, 8, 4), (1, 9, 5)):
+        ent = cases.entries(c["worlds"][world], 0, [1])
+        assert len(ent) == E and cases.table_bits(E) == bits and ent.count(m["twice"]) == 2 and sorted(set(p for p in ent if p >= 0)) == sorted(m["chain"] + m["others"])
+    home = lambda p: cases.win_home(p, 4)
+    table = cases.probe_table([p for p in cases.entries(c["worlds"][0], 0, [1]) if p >= 0], home, 16)
+    assert [home(p) for p in m["chain"]] == [14] * 5 and sorted(table[h] for h in (14, 15, 0, 1, 2)) == sorted(m["chain"]) and 3 not in table and 13 not in table
+    assert home(m["miss"]) == 15 and cases.probe_find(table, home, 16, m["miss"]) == (-1, [15, 0, 1, 2, 3]) and m["miss"] in c["worlds"][0]["slots"][2]
+    assert m["miss"] not in e[0]["point_index"] and e[0]["n_points"] == 7 and e[0]["n_fixed"] == 1
+    other = cases.probe_table([p for p in cases.entries(c["worlds"][1], 0, [1]) if p >= 0], lambda p: cases.win_home(p, 5), 32)
+    assert sorted(other) != sorted(table) and sorted(other.values()) == sorted(table.values())      # the same points in another table
+    for k in cases.WINDOW_COLUMNS:
+        assert np.asarray(e[0][k]).tobytes() == np.asarray(e[1][k]).tobytes(), k
+    c, e = size["window_mixed_call"], by["window_mixed_call"]["windows"]
+    assert [len(w["slots"]) for w in c["worlds"]] == [11, 6, 66] and len(cases.entries(c["worlds"][1], 4, [5])) == 5 and [x["usable"] for x in e] == [1, 1, 1]
+    assert e[0]["n_points"] == by["window_E_700"]["windows"][0]["n_points"] and e[2]["n_fixed"] == 64 and c["windows"][2][1] == 64
+    # -- commit
+    for name, short in (("commit_many_points", 0), ("commit_many_points_bad_capacity_short_by_one", 1)):
+        c, e = size[name], by[name]
+        win, r, m = e["windows"][0], e["commits"][0], c["marks"]
+        went = [win["point_index"].tolist().index(p) for p in BR.ba_commit(c["worlds"][0], win, win["T_c2w"], win["points"], e["flags"][0])[1]["bad_points"]]
+        assert went == m["goes_bad"] and len(went) == r["n_bad"] > 256 and {255, 256} <= set(went) and all(any(lo <= i < lo + 256 for i in went) for lo in (0, 256, 512))
+        assert r["overflow_bad"] == short and len(r["bad_points"]) == r["n_bad"] - short == c["bad_capacity"]
+        hit = set(win["obs_point"][np.flatnonzero(e["flags"][0])].tolist())
+        assert m["stays"] >= 512 and m["stays"] in hit and m["stays"] not in went and e["worlds_after"][0]["bad"][win["point_index"][m["stays"]]] == 0
+        assert win["n_points"] <= 800 and win["n_obs"] <= 3000
+    c, e = size["commit_overlap_beyond_256"], by["commit_overlap_beyond_256"]
+    a, b = e["windows"]
+    shared = set(a["point_index"].tolist()) & set(b["point_index"].tolist())
+    assert a["usable"] and b["usable"] and shared == {c["marks"]["shared"]} and not set(a["kf_index"].tolist()) & set(b["kf_index"].tolist())
+    assert a["point_index"].tolist().index(c["marks"]["shared"]) == 280 and b["point_index"].tolist().index(c["marks"]["shared"]) == 270
+    assert e["overlap"] == (0, 1) == c["overlap"] and e["commits"] == [None, None]
+    for w0, w1 in zip(c["worlds"], e["worlds_after"]):
+        cases.same_world(w0, w1, "refused")
+
+
 def test_the_chain_world_has_outliers_a_bad_point_and_a_good_point_with_an_outlier():
     """The world of the GPU chain test, solved by tests/local_ba_restatement.py: the property it was chosen for, confirmed on the CPU."""
     from tests import local_ba_restatement as R
@@ -126,7 +249,7 @@ def test_host_functions_agree_with_the_restatement(tmp_path):
     windows run in order on the map as the earlier commits left it (the overlapping case is committed by neither side)."""
     import struct
     jobs = []
-    for c in cases.all_cases():
+    for c in EVERY:
         for m, world in enumerate(c["worlds"]):
             jobs.append((c["name"], world, [kf for w, kf, _ in c["cov"] if w == m],
                          [(spec, c["outliers"].get(i, []) if c["outliers"] is not None and not c["overlap"] else None) for i, spec in enumerate(c["windows"]) if spec[0] == m]))

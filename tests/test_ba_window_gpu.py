@@ -33,8 +33,7 @@ def upload(ctx, world):
     return m
 
 
-def window_call(ctx, maps, windows):
-    room = cases.ROOM
+def window_call(ctx, maps, windows, room=cases.ROOM):
     return ba_window.WindowCall(ctx, [(maps[w], kf, cov, origin, room["kcap"] if kc is None else kc, room["pcap"] if pc is None else pc,
                                        room["ocap"] if oc is None else oc) for w, kf, cov, origin, kc, pc, oc in windows])
 
@@ -87,7 +86,7 @@ def outlier_tensor(call, flags):
     return torch.from_numpy(host).to("cuda:0")
 
 
-@pytest.mark.parametrize("c", cases.all_cases(), ids=lambda c: c["name"])
+@pytest.mark.parametrize("c", cases.all_cases() + cases.size_cases(), ids=lambda c: c["name"])
 def test_every_case_equals_the_restatement(mp_ctx, c):
     import torch
     want = cases.expected(c)
@@ -102,11 +101,12 @@ def test_every_case_equals_the_restatement(mp_ctx, c):
                     assert np.all(raw.view(np.uint8)[4 * min(e["n_cov"], cap):] == ba_window.FILL)
         if not c["windows"]:
             return
-        call = window_call(mp_ctx, maps, c["windows"])
+        call = window_call(mp_ctx, maps, c["windows"], c["room"])
         got = call.run()
         check_windows(call, got, want["windows"], c["name"])
         if c["outliers"] is None:
             return
+        bad_capacity = 8 if c["bad_capacity"] is None else c["bad_capacity"]        # (the rule-edge cases turn at most 4 points bad)
         # the commit: the restated one takes the same moved poses and points
         values = moved(call, want["windows"])
         worlds = [copy.deepcopy(w) for w in c["worlds"]]
@@ -116,9 +116,9 @@ def test_every_case_equals_the_restatement(mp_ctx, c):
                 restated.append(None)
                 continue
             m = c["windows"][i][0]
-            worlds[m], r = cases.BR.ba_commit(worlds[m], w, values[i][0], values[i][1], want["flags"][i])
+            worlds[m], r = cases.BR.ba_commit(worlds[m], w, values[i][0], values[i][1], want["flags"][i], c["bad_capacity"])
             restated.append(r)
-        st, res = call.commit(outlier_tensor(call, want["flags"]), torch.cuda.current_stream().cuda_stream, bad_capacity=8)
+        st, res = call.commit(outlier_tensor(call, want["flags"]), torch.cuda.current_stream().cuda_stream, bad_capacity=bad_capacity)
         if want["overlap"]:
             a, b = want["overlap"]
             assert c["overlap"] == want["overlap"] and st == INVALID and f"windows {a} and {b}" in mp_ctx.last_error(), (st, mp_ctx.last_error())
@@ -178,6 +178,34 @@ def test_a_window_alone_and_as_one_of_eight_gives_the_same_bytes(mp_ctx):
     assert np.all(call.column("obs_slot")[at["obs"] + w["n_obs"]:at["obs"] + cases.ROOM["ocap"]].view(np.uint8) == ba_window.FILL)
     for m in maps:
         m.close()
+
+
+def test_windows_of_very_different_sizes_in_one_call_equal_each_alone(mp_ctx):
+    """window_mixed_call: a 700-entry window, a 5-entry window on a 6-keyframe map and a window on a 66-keyframe map share every launch
+    (the grids are sized by the largest; the small ones' extra workgroups must return): each result is byte-equal to the same window
+    run alone, and behind each window's counts the fill bytes stand."""
+    c = cases.by_name("window_mixed_call")
+    want = cases.expected(c)["windows"]
+    maps = [upload(mp_ctx, w) for w in c["worlds"]]
+    try:
+        call = window_call(mp_ctx, maps, c["windows"], c["room"])
+        got = call.run()
+        check_windows(call, got, want, c["name"])
+        cap = dict(kf=c["room"]["kcap"], point=c["room"]["pcap"], obs=c["room"]["ocap"])
+        whole = {name: call.column(name) for name, _, _, _ in ba_window.DEVICE_ARRAYS}
+        for i, spec in enumerate(c["windows"]):
+            alone = window_call(mp_ctx, maps, [spec], c["room"]).run()[0]
+            for k in cases.WINDOW_COLUMNS:
+                assert np.asarray(alone[k]).tobytes() == np.asarray(got[i][k]).tobytes(), (i, k)
+            for f in ba_window.RESULT_FIELDS:
+                assert alone[f] == got[i][f], (i, f)
+            cnt = dict(kf=want[i]["n_local"] + want[i]["n_fixed"], point=want[i]["n_points"], obs=want[i]["n_obs"])
+            for name, _, _, by in ba_window.DEVICE_ARRAYS:
+                at = call.offsets[i][by]
+                assert np.all(whole[name][at + cnt[by]:at + cap[by]].view(np.uint8) == ba_window.FILL), (i, name)
+    finally:
+        for m in maps:
+            m.close()
 
 
 def test_local_after_a_commit_sees_moved_points_and_no_bad_ones(mp_ctx):
