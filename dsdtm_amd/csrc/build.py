@@ -76,6 +76,10 @@ ADDONS = {
               os.path.join(_INC, "dsdtm_amd_trackmap.h"), os.path.join(_INC, "dsdtm_amd_localmap.h"), os.path.join(_INC, "dsdtm_amd_keyframe.h"),
               os.path.join(_INC, "dsdtm_amd.h")],
              os.path.join(HERE, "libdsdtm_amd_slam.so")),
+    # include/dsdtm_amd_undistort.h: cv::undistort of raw gray / depth frames and Frame::UndistortFeatures, in front of dsdtm_frame_prefetch
+    "undistort": (["undistort_api.cpp", "undistort.hip"],
+                  ["undistort.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_undistort.h"), os.path.join(_INC, "dsdtm_amd.h")],
+                  os.path.join(HERE, "libdsdtm_amd_undistort.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")

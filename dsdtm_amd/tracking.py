@@ -253,9 +253,10 @@ class Tracker:
     pose; matched map points IncreaseFound (src/Feature_alignment.cpp:106); the mask gets its discs (:111); PoseOptimization's
     EraseFound walk runs on the block-ordered norms (src/Optimizer.cpp:80-92)."""
 
-    def __init__(self, camera, ctx: capi.Context | None = None, max_level=None, min_level=None, max_iters=None, min_tracked=20):
+    def __init__(self, camera, ctx: capi.Context | None = None, max_level=None, min_level=None, max_iters=None, min_tracked=20, distortion=None):
         self.cam = camera
         self.ctx = ctx or capi.default_context()
+        self.distortion = None if distortion is None else tuple(float(v) for v in distortion)          # k1 k2 p1 p2 k3 (src/Camera.cpp:62-67); None: rectified images
         self.levels = int(Config.Get("Camera.MaxPyraLevels") if max_level is None else max_level)       # src/Tracking.cpp:20-24
         self.min_level = int(Config.Get("Camera.MinPyraLevels") if min_level is None else min_level)
         self.max_iters = int(Config.Get("Optimization.MaxIter") if max_iters is None else max_iters)
@@ -276,6 +277,56 @@ class Tracker:
             self._prefetched.pop(0)[1].close()
         return df
 
+    def _undistort(self):
+        """The undistort add-on's context and this camera's map (built once), where a distortion was given."""
+        from . import undistort
+        if self.distortion is None:
+            raise ValueError("this Tracker was made without a distortion: its images are rectified already")
+        if getattr(self, "_undistort_ctx", None) is None:
+            self._undistort_ctx = undistort.UndistortContext(self.ctx.device if hasattr(self.ctx, "device") else 0)
+            self._undistort_map = self._undistort_ctx.make_map(self.cam, self.distortion)
+        return self._undistort_ctx, self._undistort_map
+
+    def prefetch_raw(self, image, depth=None, depth_scale: float = 5000.0):
+        """prefetch() for a RAW sensor frame (a Tracker made with `distortion`): cv::undistort, which the reference switched off for its
+        cost (src/Frame.cpp:57-61), through dsdtm_undistort_frames into torch device tensors, then the existing prefetch on their
+        data_ptr(). `image` (uint8) and `depth` (uint16 or None): 2-D numpy arrays or torch tensors. TrackFrame(image, ...) with the
+        same image object starts at Run on the rectified frame, and the Frame it returns is marked `rectified`: CraeteKeyframe does
+        not move its features a second time (prefetch_raw and UndistortFeatures are ALTERNATIVES: the image is rectified, or the
+        features detected on a raw image are). The Frame object keeps the caller's RAW host image; the rectified one is the returned
+        tensor. Returns (capi.DeviceFrame, rectified gray, rectified depth (int16 holding the uint16 bytes) or None); the tensors
+        stay alive with the frame."""
+        import torch
+        uctx, umap = self._undistort()
+        dev = torch.device("cuda", uctx.device)
+        h, w = umap.height, umap.width
+        gray_t = torch.empty((h, w), dtype=torch.uint8, device=dev)
+        depth_t = torch.empty((h, w), dtype=torch.int16, device=dev) if depth is not None else None      # (int16: the bytes of uint16)
+        torch.cuda.synchronize(dev)              # (the tensors exist; the add-on's stream is its own)
+        uctx.undistort_frames([dict(map=umap, gray_src=image, gray_dst=gray_t, depth_src=depth, depth_dst=depth_t)])
+        df = capi.DeviceFrame.prefetch(self.ctx, (gray_t.data_ptr(), w, h, gray_t.stride(0)), self.levels,
+                                       None if depth_t is None else (depth_t.data_ptr(), depth_t.stride(0)), depth_scale)
+        df._keep = [gray_t, depth_t]
+        df.rectified = True
+        self._prefetched.append((image, df))
+        while len(self._prefetched) > 2:
+            self._prefetched.pop(0)[1].close()
+        return df, gray_t, depth_t
+
+    def UndistortFeatures(self, frame):
+        """Frame::UndistortFeatures (src/Frame.cpp:94-150) on `frame`: the pixel of every feature that is not mbInitial goes through
+        cv::undistortPoints(.., K, D, noArray(), K) (rule U5 of include/dsdtm_amd_undistort.h) and its bearing is recomputed, through
+        dsdtm_undistort_points. (The C++ adapter evaluates undistort_points_host for one tracker, which is faster there; that
+        function has no Python binding, and numpy is slower than the device call: profiles/r22_undistort.txt.) Nothing happens
+        without a distortion, on a frame without features, and on a frame that came through prefetch_raw (its image was rectified:
+        its features lie on the rectified image already)."""
+        if self.distortion is None or frame.n_features == 0 or getattr(frame, "rectified", False):
+            return frame
+        uctx, _ = self._undistort()
+        px, _ = uctx.undistort_points(self.cam, self.distortion, frame.px, frame.initial, bearing_out=frame.bearing)
+        frame.px[:] = px
+        return frame
+
     def TrackFrame(self, image, last: Frame, keyframes, map_points, img_mask=None):
         """Returns (cur Frame, n_tracked, matches as [(cell, MapPoint, px float32[2], level)])."""
         cur_frame = None
@@ -290,6 +341,8 @@ class Tracker:
                         keyframes, map_points, mask=img_mask, cur_frame=cur_frame)
         self.last_result = r
         out = apply_tracked_frame(self.cam, image, r, map_points, img_mask)
+        if getattr(cur_frame, "rectified", False):          # (from prefetch_raw)
+            out[0].rectified = True
         self.last_frame = out[0]
         return out
 
@@ -320,7 +373,10 @@ class Tracker:
         cur = cur if cur is not None else self.last_frame
         if cur is None:
             raise ValueError("CraeteKeyframe: no frame was given and TrackFrame has not returned one yet")
-        return kc.create_keyframes(self.ctx, nctx, self.cam, [cur], [store], [depth], depth_scale)[0]
+        out = kc.create_keyframes(self.ctx, nctx, self.cam, [cur], [store], [depth], depth_scale)[0]
+        if self.distortion is not None:          # src/Tracking.cpp:417 (here behind the lift, which the one device call includes)
+            self.UndistortFeatures(cur)
+        return out
 
     def CreateInitialMapRGBD(self, store, depth, init_frame, depth_scale: float = 5000.0):
         """Tracking::CreateInitialMapRGBD (src/Tracking.cpp:147-196): CraeteKeyframe's call on a frame without features, plus the
@@ -328,6 +384,8 @@ class Tracker:
         kc, nctx = self._newkf()
         if init_frame.n_features:
             raise ValueError("the initial frame has features already")
+        if self.distortion is not None:          # src/Tracking.cpp:149 (a frame without features: nothing to move)
+            self.UndistortFeatures(init_frame)
         return kc.create_keyframes(self.ctx, nctx, self.cam, [init_frame], [store], [depth], depth_scale, min_points=100)[0]
 
     def UpdateLocalMap(self, store, T, n_local: int = 10):
