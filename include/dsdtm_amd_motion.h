@@ -13,8 +13,8 @@
  *           Tracking::MotionRemoval (src/Tracking.cpp:487-512) calls these on every tracked frame — in the reference as it stands that
  *           call is COMMENTED OUT (src/Tracking.cpp:230), so this is the stage the reference's authors wrote, not one it runs.
  * OUT OF SCOPE: cv::findHomography and its RANSAC (the caller's; H is an argument); the contour step of MCDWrapper::Run (:98-128: the
- *           bounding rectangle of the largest contourArea contour filled into the mask — it cannot be restated faithfully without
- *           OpenCV's findContours, so `mask` is detect_img BEFORE it); KLTWrapper (initialised at :75, never used on this path);
+ *           bounding rectangle of the largest contourArea contour filled into the mask — `mask` here is detect_img BEFORE it; the
+ *           whole Run, that step included, is libdsdtm_amd_mcd.so's, include/dsdtm_amd_mcd.h); KLTWrapper (initialised at :75, never used on this path);
  *           Moving_Detecter::Mod_FrameDiff; dsdtm_track_frame, which is unchanged and knows nothing of this library.
  */
 #ifndef DSDTM_AMD_MOTION_H
