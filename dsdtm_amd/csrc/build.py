@@ -90,6 +90,12 @@ MORE_ADDONS = {
             ["contour.h", "motion_api_body.h", "motion.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_mcd.h"),
              os.path.join(_INC, "dsdtm_amd_motion.h"), os.path.join(_INC, "dsdtm_amd.h")],
             os.path.join(HERE, "libdsdtm_amd_mcd.so")),
+    # include/dsdtm_amd_klt.h: KLTWrapper::RunTrack — the grid's pyramidal Lucas-Kanade flow (klt.hip) and the H of the survivors
+    # (homography.hip and pyrdown.hip are linked as they are)
+    "klt": (["klt_api.cpp", "klt.hip", "homography.hip", "pyrdown.hip"],
+            ["klt.h", "homography.h", "kernels.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_klt.h"),
+             os.path.join(_INC, "dsdtm_amd_homography.h"), os.path.join(_INC, "dsdtm_amd.h")],
+            os.path.join(HERE, "libdsdtm_amd_klt.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")

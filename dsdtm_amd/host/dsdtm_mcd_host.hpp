@@ -130,6 +130,16 @@ public:
         if (out) *out = std::move(m);
         return true;
     }
+    // The same without an H argument, as MCDWrapper::Run works: `klt` (a DSDTM::KLTWrapper of dsdtm_klt_host.hpp, which the caller owns and
+    // includes) tracks its grid from the last image into this one and its H goes into the step above. The first image seeds it (identity).
+    template <class Klt>
+    bool Mod_FastMCD_KLT(const uint8_t* gray, int width, int height, int stride, Klt& klt, const std::vector<Feature2f>& features, Mask* out) {
+        if (required_rows_ && height != required_rows_) return false;
+        klt.RunTrack(gray, width, height, stride);
+        double H[9];
+        klt.GetHomography(H);
+        return Mod_FastMCD(gray, width, height, stride, (const double*)H, features, out);
+    }
     std::vector<Feature2f> Motion_Removal(const std::vector<Feature2f>& features, bool faithful = true) const {
         if (features.size() != on_mask_.size()) throw std::runtime_error("Motion_Removal: not the features the last Mod_FastMCD was given");
         std::vector<Feature2f> out;

@@ -1,0 +1,196 @@
+"""KLTWrapper::RunTrack (Thirdparty/fastMCD/src/KLTWrapper.cpp:112-189) restated in numpy: rules K1-K9 of include/dsdtm_amd_klt.h,
+written for reading. The pyramidal Lucas-Kanade of a grid of points from the previous gray image into the current one, and the RANSAC
+homography (dsdtm_amd/homography_restatement.py) of the points that survived. OpenCV is not available to this project: what is kept
+is the documented shape of the call at KLTWrapper.cpp:125-126; everything else is this project's definition, and this file is its
+yardstick (the device, and klt_flow_host of dsdtm_amd/host/dsdtm_klt_host.hpp, are bit-equal to it).
+
+Every sum over a window is an integer sum (Python ints / int64), so its order is free. The only floating point is the scalar tail of
+an iteration, IEEE double in the written order. A class: the mutants of tests/test_klt_cpu.py override one method each.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import homography_restatement as HR
+from .synth import build_pyramid
+
+W_BITS = 14
+ONE = 1 << W_BITS
+SCALE = 1.0 / (1 << 20)                       # K5: what an integer window sum is multiplied by on its way to double
+FLT_EPSILON = 1.1920928955078125e-07
+DEFAULT_WINDOW, DEFAULT_LEVELS, DEFAULT_ITERATIONS, DEFAULT_EPSILON, DEFAULT_MIN_EIG = 10, 4, 20, 0.03, 1e-4
+MIN_TRACKED = 10                              # KLTWrapper.cpp:138: fewer tracked points than this give the identity
+RANSAC_THRESHOLD = 1.0                        # KLTWrapper.cpp:180
+SOURCE_IDENTITY, SOURCE_RANSAC, SOURCE_KEPT = 0, 1, 2
+IDENTITY = np.array([1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0])
+
+
+def grid_points(width, height, gw=0, gh=0):
+    """K8: the points InitFeatures writes (KLTWrapper.cpp:102-107), i major. NOT the reference's count (:99), see the header."""
+    gw, gh = gw or 32, gh or 24
+    return np.array([(i * gw + gw // 2, j * gh + gh // 2) for i in range(width // gw - 1) for j in range(height // gh - 1)],
+                    np.float32).reshape(-1, 2)
+
+
+def weights(fx, fy):
+    """K3: the four fixed-point weights of the fractional position (fx, fy), each in 1/2^14; round half up, the last by difference."""
+    w00 = int(math.floor((1.0 - fx) * (1.0 - fy) * ONE + 0.5))
+    w01 = int(math.floor(fx * (1.0 - fy) * ONE + 0.5))
+    w10 = int(math.floor((1.0 - fx) * fy * ONE + 0.5))
+    return w00, w01, w10, ONE - w00 - w01 - w10
+
+
+def bilinear(img, ix, iy, n, w, shift):
+    """K3: the n x n window whose top-left tap is (ix, iy) of an integer image, weights w, rounded to `shift` bits less."""
+    a = img[iy:iy + n + 1, ix:ix + n + 1].astype(np.int64)
+    s = a[:-1, :-1] * w[0] + a[:-1, 1:] * w[1] + a[1:, :-1] * w[2] + a[1:, 1:] * w[3]
+    return (s + (1 << (shift - 1))) >> shift
+
+
+class Klt:
+    KERNEL = (3, 10, 3)                         # K2: Scharr
+
+    def gradients(self, level):
+        """K2: integer derivative images of a u8 level; the 1-pixel border is never read by a window that passed K4."""
+        a = level.astype(np.int64)
+        k0, k1, k2 = self.KERNEL
+        gx = np.zeros_like(a)
+        gy = np.zeros_like(a)
+        gx[1:-1, 1:-1] = (k0 * (a[:-2, 2:] - a[:-2, :-2]) + k1 * (a[1:-1, 2:] - a[1:-1, :-2]) + k2 * (a[2:, 2:] - a[2:, :-2]))
+        gy[1:-1, 1:-1] = (k0 * (a[2:, :-2] - a[:-2, :-2]) + k1 * (a[2:, 1:-1] - a[:-2, 1:-1]) + k2 * (a[2:, 2:] - a[:-2, 2:]))
+        return gx, gy
+
+    def ring(self):
+        return 1                                # K4: the previous window counts the Scharr ring
+
+    def stops(self, d2, eps2):
+        return d2 <= eps2                       # K6: <=, not <
+
+    def halves_on_oscillation(self):
+        return True                             # K6
+
+    def oriented(self, cur, prev):
+        return cur, prev                        # K9: A = current, B = previous
+
+    def keeps_stale_h(self):
+        return True                             # K9: MakeHomoGraphy returns without writing matH
+
+    def inside(self, ix, iy, n, w, h, ring):
+        return ix - ring >= 0 and iy - ring >= 0 and ix + n + ring <= w - 1 and iy + n + ring <= h - 1
+
+    def track_point(self, prev_pyr, cur_pyr, grads, p, guess, window, iterations, eps, min_eig):
+        """One point through the levels, coarsest first. -> (x, y, status, iterations used, residual)."""
+        levels = len(prev_pyr)
+        half = (window - 1) * 0.5
+        eps2 = eps * eps
+        top = float(1 << (levels - 1))
+        nx, ny = float(guess[0]) / top, float(guess[1]) / top
+        used, status, residual = 0, 1, 0.0
+        for l in range(levels - 1, -1, -1):
+            I, J = prev_pyr[l], cur_pyr[l]
+            h, w = I.shape
+            s = float(1 << l)
+            px, py = float(p[0]) / s - half, float(p[1]) / s - half
+            ix, iy = math.floor(px), math.floor(py)
+            if l < levels - 1:
+                nx, ny = nx * 2.0, ny * 2.0         # K7: the hand-down
+            if not self.inside(ix, iy, window, w, h, self.ring()):
+                if l == 0:
+                    status = 0
+                continue                            # K4: a coarser level is skipped, the guess is handed down
+            wt = weights(px - ix, py - iy)
+            gx, gy = grads[l]
+            Iw = bilinear(I, ix, iy, window, wt, W_BITS - 5)
+            dx = bilinear(gx, ix, iy, window, wt, W_BITS)
+            dy = bilinear(gy, ix, iy, window, wt, W_BITS)
+            a11 = float(int((dx * dx).sum())) * SCALE
+            a12 = float(int((dx * dy).sum())) * SCALE
+            a22 = float(int((dy * dy).sum())) * SCALE
+            det = a11 * a22 - a12 * a12
+            min_e = (a22 + a11 - math.sqrt((a11 - a22) * (a11 - a22) + 4.0 * a12 * a12)) / (2.0 * (window * window))
+            if min_e < min_eig or det < FLT_EPSILON:
+                if l == 0:
+                    status = 0
+                continue                            # K5
+            inv = 1.0 / det
+            qx, qy = nx - half, ny - half
+            pdx = pdy = 0.0
+            for j in range(iterations):
+                jx, jy = math.floor(qx), math.floor(qy)
+                if not self.inside(jx, jy, window, w, h, 0):
+                    if l == 0:
+                        status = 0
+                    break
+                wj = weights(qx - jx, qy - jy)
+                diff = bilinear(J, jx, jy, window, wj, W_BITS - 5) - Iw
+                b1 = float(int((diff * dx).sum())) * SCALE
+                b2 = float(int((diff * dy).sum())) * SCALE
+                ddx = (a12 * b2 - a22 * b1) * inv
+                ddy = (a12 * b1 - a11 * b2) * inv
+                qx, qy = qx + ddx, qy + ddy
+                used += 1
+                if self.stops(ddx * ddx + ddy * ddy, eps2):
+                    break
+                if j > 0 and abs(ddx + pdx) < 0.01 and abs(ddy + pdy) < 0.01 and self.halves_on_oscillation():
+                    qx, qy = qx - ddx * 0.5, qy - ddy * 0.5
+                    break
+                pdx, pdy = ddx, ddy
+            nx, ny = qx + half, qy + half
+            if l == 0 and status == 1:              # K7: the residual, and the last look at the border
+                jx, jy = math.floor(qx), math.floor(qy)
+                if not self.inside(jx, jy, window, w, h, 0):
+                    status = 0
+                else:
+                    diff = bilinear(J, jx, jy, window, weights(qx - jx, qy - jy), W_BITS - 5) - Iw
+                    residual = float(int(np.abs(diff).sum())) / (32.0 * (window * window))
+        return np.float32(nx), np.float32(ny), status, used, np.float32(residual if status else 0.0)
+
+    def flow(self, prev, cur, points, guesses=None, window=DEFAULT_WINDOW, levels=DEFAULT_LEVELS, iterations=DEFAULT_ITERATIONS,
+             eps=DEFAULT_EPSILON, min_eig=DEFAULT_MIN_EIG):
+        """calcOpticalFlowPyrLK. prev / cur: u8 images, or pyramids (lists of levels). -> dict(points, status, iterations, residual)."""
+        prev_pyr = prev if isinstance(prev, list) else build_pyramid(prev, levels)
+        cur_pyr = cur if isinstance(cur, list) else build_pyramid(cur, levels)
+        grads = [self.gradients(l) for l in prev_pyr]
+        pts = np.asarray(points, np.float32).reshape(-1, 2)
+        g = pts if guesses is None else np.asarray(guesses, np.float32).reshape(-1, 2)
+        out = [self.track_point(prev_pyr, cur_pyr, grads, pts[k], g[k], window, iterations, eps, min_eig) for k in range(len(pts))]
+        return dict(points=np.array([(o[0], o[1]) for o in out], np.float32).reshape(-1, 2), status=np.array([o[2] for o in out], np.uint8),
+                    iterations=np.array([o[3] for o in out], np.int32), residual=np.array([o[4] for o in out], np.float32))
+
+
+class KltModel:
+    """The state RunTrack carries from frame to frame: the previous pyramid, the previous H, the frame counter."""
+
+    def __init__(self, width, height, levels=DEFAULT_LEVELS, gw=0, gh=0, klt=None, ransac=None):
+        self.width, self.height, self.levels = width, height, levels
+        self.klt, self.ransac = klt or Klt(), ransac or HR.Ransac()
+        self.gw, self.gh = gw, gh
+        self.grid = grid_points(width, height, gw, gh)
+        self.reset()
+
+    def reset(self):
+        self.prev, self.H, self.frames = None, IDENTITY.copy(), 0
+
+    def step(self, image, gw=None, gh=None):
+        """RunTrack (gw / gh: another grid for this step alone, K8). -> dict(H, source, n_points, n_tracked, n_inliers, prev_points, points, status, iterations, mask, ransac)."""
+        cur = build_pyramid(np.ascontiguousarray(image, np.uint8), self.levels)
+        self.grid = grid_points(self.width, self.height, gw or self.gw, gh or self.gh)
+        n = len(self.grid)
+        r = dict(H=IDENTITY.copy(), source=SOURCE_IDENTITY, n_points=n, n_tracked=0, n_inliers=0, prev_points=self.grid.copy(),
+                 points=self.grid.copy(), status=np.zeros(n, np.uint8), iterations=np.zeros(n, np.int32), mask=np.zeros(0, np.uint8), ransac=None)
+        if self.prev is not None:
+            f = self.klt.flow(self.prev, cur, self.grid, levels=self.levels)
+            keep = np.flatnonzero(f["status"])
+            r.update(points=f["points"], status=f["status"], iterations=f["iterations"], n_tracked=len(keep))
+            if len(keep) >= MIN_TRACKED:
+                A, B = self.klt.oriented(f["points"][keep], self.grid[keep])
+                got = self.ransac.find(A, B, thr=RANSAC_THRESHOLD)
+                r["ransac"] = got
+                if got["found"] == 1:
+                    r.update(H=np.array(got["H"], np.float64), source=SOURCE_RANSAC, n_inliers=int(got["n_inliers"]), mask=np.asarray(got["mask"], np.uint8))
+                elif self.klt.keeps_stale_h():
+                    r.update(H=self.H.copy(), source=SOURCE_KEPT)
+        self.prev, self.H, self.frames = cur, r["H"].copy(), self.frames + 1
+        return r

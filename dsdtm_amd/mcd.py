@@ -221,6 +221,16 @@ class MotionDetector:
 
     Mod_FastMCD = Run
 
+    def RunTrack(self, image, features=None, want_raw=False) -> np.ndarray:
+        """Run without an H argument, as MCDWrapper::Run works: a KLTWrapper (dsdtm_amd/klt.py, libdsdtm_amd_klt.so; made on first use,
+        on this detector's device) tracks its grid from the last image into this one, and its H goes into Run. The first image seeds
+        it (identity). self.klt.last holds the step's result (source, n_tracked, n_inliers)."""
+        if getattr(self, "klt", None) is None:
+            from . import klt as _klt
+            self.klt = _klt.KLTWrapper(device=self.ctx.device)
+        self.klt.RunTrack(image)
+        return self.Run(image, self.klt.GetHomography().reshape(9), features=features, want_raw=want_raw)
+
     def motion_removal(self, features):
         """Frame::Motion_Removal against the last image Run returned: (keep, rebuilt), as dsdtm_amd.motion.MovingDetector.motion_removal."""
         f = np.asarray(features, np.float32).reshape(-1, 2)
