@@ -80,8 +80,12 @@ class Klt:
     def inside(self, ix, iy, n, w, h, ring):
         return ix - ring >= 0 and iy - ring >= 0 and ix + n + ring <= w - 1 and iy + n + ring <= h - 1
 
-    def track_point(self, prev_pyr, cur_pyr, grads, p, guess, window, iterations, eps, min_eig):
-        """One point through the levels, coarsest first. -> (x, y, status, iterations used, residual)."""
+    def track_point(self, prev_pyr, cur_pyr, grads, p, guess, window, iterations, eps, min_eig, trace=None):
+        """One point through the levels, coarsest first. -> (x, y, status, iterations used, residual).
+        trace: None, or a list that gets one dict(level, exit, steps, s11, s12, s22, t1, t2) per level, in the order the levels are
+        visited: how the level was left (prev_outside, eigen, cur_outside, eps, oscillation, cap), after how many iterations, its integer
+        totals and the largest |sum d dx|, |sum d dy| of its iterations (with their signs: t1_min, t1_max, t2_min, t2_max), and one more entry `final_outside` where K7's
+        last look fails. Nothing of the result depends on it."""
         levels = len(prev_pyr)
         half = (window - 1) * 0.5
         eps2 = eps * eps
@@ -96,6 +100,9 @@ class Klt:
             ix, iy = math.floor(px), math.floor(py)
             if l < levels - 1:
                 nx, ny = nx * 2.0, ny * 2.0         # K7: the hand-down
+            note = dict(level=l, exit="prev_outside", s11=0, s12=0, s22=0, steps=0, t1=0, t2=0, t1_min=0, t1_max=0, t2_min=0, t2_max=0)
+            if trace is not None:
+                trace.append(note)
             if not self.inside(ix, iy, window, w, h, self.ring()):
                 if l == 0:
                     status = 0
@@ -105,9 +112,11 @@ class Klt:
             Iw = bilinear(I, ix, iy, window, wt, W_BITS - 5)
             dx = bilinear(gx, ix, iy, window, wt, W_BITS)
             dy = bilinear(gy, ix, iy, window, wt, W_BITS)
-            a11 = float(int((dx * dx).sum())) * SCALE
-            a12 = float(int((dx * dy).sum())) * SCALE
-            a22 = float(int((dy * dy).sum())) * SCALE
+            s11, s12, s22 = int((dx * dx).sum()), int((dx * dy).sum()), int((dy * dy).sum())
+            note.update(exit="eigen", s11=s11, s12=s12, s22=s22)
+            a11 = float(s11) * SCALE
+            a12 = float(s12) * SCALE
+            a22 = float(s22) * SCALE
             det = a11 * a22 - a12 * a12
             min_e = (a22 + a11 - math.sqrt((a11 - a22) * (a11 - a22) + 4.0 * a12 * a12)) / (2.0 * (window * window))
             if min_e < min_eig or det < FLT_EPSILON:
@@ -117,24 +126,32 @@ class Klt:
             inv = 1.0 / det
             qx, qy = nx - half, ny - half
             pdx = pdy = 0.0
+            note["exit"] = "cap"
             for j in range(iterations):
                 jx, jy = math.floor(qx), math.floor(qy)
                 if not self.inside(jx, jy, window, w, h, 0):
                     if l == 0:
                         status = 0
+                    note["exit"] = "cur_outside"
                     break
                 wj = weights(qx - jx, qy - jy)
                 diff = bilinear(J, jx, jy, window, wj, W_BITS - 5) - Iw
-                b1 = float(int((diff * dx).sum())) * SCALE
-                b2 = float(int((diff * dy).sum())) * SCALE
+                t1, t2 = int((diff * dx).sum()), int((diff * dy).sum())
+                note.update(t1=max(note["t1"], abs(t1)), t2=max(note["t2"], abs(t2)), t1_min=min(note["t1_min"], t1), t1_max=max(note["t1_max"], t1),
+                            t2_min=min(note["t2_min"], t2), t2_max=max(note["t2_max"], t2))
+                b1 = float(t1) * SCALE
+                b2 = float(t2) * SCALE
                 ddx = (a12 * b2 - a22 * b1) * inv
                 ddy = (a12 * b1 - a11 * b2) * inv
                 qx, qy = qx + ddx, qy + ddy
                 used += 1
+                note["steps"] += 1
                 if self.stops(ddx * ddx + ddy * ddy, eps2):
+                    note["exit"] = "eps"
                     break
                 if j > 0 and abs(ddx + pdx) < 0.01 and abs(ddy + pdy) < 0.01 and self.halves_on_oscillation():
                     qx, qy = qx - ddx * 0.5, qy - ddy * 0.5
+                    note["exit"] = "oscillation"
                     break
                 pdx, pdy = ddx, ddy
             nx, ny = qx + half, qy + half
@@ -142,20 +159,28 @@ class Klt:
                 jx, jy = math.floor(qx), math.floor(qy)
                 if not self.inside(jx, jy, window, w, h, 0):
                     status = 0
+                    if trace is not None:
+                        trace.append(dict(note, exit="final_outside"))
                 else:
                     diff = bilinear(J, jx, jy, window, weights(qx - jx, qy - jy), W_BITS - 5) - Iw
                     residual = float(int(np.abs(diff).sum())) / (32.0 * (window * window))
         return np.float32(nx), np.float32(ny), status, used, np.float32(residual if status else 0.0)
 
     def flow(self, prev, cur, points, guesses=None, window=DEFAULT_WINDOW, levels=DEFAULT_LEVELS, iterations=DEFAULT_ITERATIONS,
-             eps=DEFAULT_EPSILON, min_eig=DEFAULT_MIN_EIG):
-        """calcOpticalFlowPyrLK. prev / cur: u8 images, or pyramids (lists of levels). -> dict(points, status, iterations, residual)."""
+             eps=DEFAULT_EPSILON, min_eig=DEFAULT_MIN_EIG, trace=None):
+        """calcOpticalFlowPyrLK. prev / cur: u8 images, or pyramids (lists of levels). -> dict(points, status, iterations, residual).
+        trace: None, or a list that gets track_point's entries, each with `point` (the index) and `status` (the point's final one)."""
         prev_pyr = prev if isinstance(prev, list) else build_pyramid(prev, levels)
         cur_pyr = cur if isinstance(cur, list) else build_pyramid(cur, levels)
         grads = [self.gradients(l) for l in prev_pyr]
         pts = np.asarray(points, np.float32).reshape(-1, 2)
         g = pts if guesses is None else np.asarray(guesses, np.float32).reshape(-1, 2)
-        out = [self.track_point(prev_pyr, cur_pyr, grads, pts[k], g[k], window, iterations, eps, min_eig) for k in range(len(pts))]
+        out = []
+        for k in range(len(pts)):
+            notes = None if trace is None else []
+            out.append(self.track_point(prev_pyr, cur_pyr, grads, pts[k], g[k], window, iterations, eps, min_eig, trace=notes))
+            if trace is not None:
+                trace.extend(dict(e, point=k, status=out[-1][2]) for e in notes)
         return dict(points=np.array([(o[0], o[1]) for o in out], np.float32).reshape(-1, 2), status=np.array([o[2] for o in out], np.uint8),
                     iterations=np.array([o[3] for o in out], np.int32), residual=np.array([o[4] for o in out], np.float32))
 

@@ -330,6 +330,198 @@ def test_mutant_stale_h_fixed():
         assert np.array_equal(r2["H"], r1["H"] if source == KR.SOURCE_KEPT else KR.IDENTITY)
 
 
+# ---- the worlds of the device's edge tests, held to their claims ---------------------------------------------------------------------
+# (saturated contrast, windows around a pass of 64 lanes, every exit of the two loops, the compaction's edges: tests/test_klt_gpu.py
+#  runs them on the device; here the restatement's trace says what they reach, and klt_flow_host agrees with it bit for bit. The host
+#  function takes every parameter these worlds use — any window, level count, iteration cap and epsilon, guesses — so nothing is left out
+#  of that comparison; klt_step_host has the defaults of RunTrack built in, which are the compaction worlds' parameters.)
+
+SATURATED_WINDOWS = (21, 16, 10, 4)
+
+
+def _plain_sum(v):
+    return int(v.sum())
+
+
+def test_saturated_worlds_carry_past_31_and_32_bits(host):
+    """Window 21, from the trace, over points with status 1: an s11 or s22 above 2^31 on every world, a t1 / t2 above 2^32 in magnitude
+    with both signs over the worlds, and |dx| = 4080 on the block noise."""
+    beyond = []
+    for name, prev, cur in cases.saturated_worlds():
+        pts = cases.saturated_points(21)
+        tr = []
+        f = K.flow(prev, cur, pts, window=21, levels=1, trace=tr)
+        assert cases.same_flow(cases.host_flow(host, prev, cur, pts, window=21, levels=1), f)
+        ok = [e for e in tr if e["status"] == 1]
+        assert f["status"][:7].all() and ok, name                  # the interior points track
+        assert max(max(e["s11"], e["s22"]) for e in ok) > 2 ** 31, name
+        beyond += [e["t1_min"] for e in ok] + [e["t1_max"] for e in ok] + [e["t2_min"] for e in ok] + [e["t2_max"] for e in ok]
+        with cases.observed_sums(_plain_sum) as seen:
+            again = K.flow(prev, cur, pts[f["status"] == 1], window=21, levels=1)
+        assert again["status"].all()
+        print(name, "s max", max(max(e["s11"], e["s22"]) for e in ok), "t1", min(e["t1_min"] for e in ok), max(e["t1_max"] for e in ok), "|dx|", seen.gradient_max)
+        assert seen.gradient_max == (4080 if name.startswith("noise") else 2550), (name, seen.gradient_max)
+    assert min(beyond) < -2 ** 32 and max(beyond) > 2 ** 32, (min(beyond), max(beyond))
+    tr = []
+    K.flow(*cases.checker_world(), [(80, 60)], window=21, levels=1, trace=tr)          # the figures of the world's docstring
+    assert (tr[0]["s11"], tr[0]["s22"], tr[0]["t1_min"], tr[0]["steps"], tr[0]["status"]) == (2867602500, 2867602500, -4806648000, 8, 1)
+
+
+@pytest.mark.parametrize("window", SATURATED_WINDOWS)
+def test_a_lanes_partial_sum_fits_32_bits_on_the_saturated_worlds(window):
+    """klt_kernel keeps a lane's partial of dx dx, dx dy, dy dy, d dx, d dy and |d| in an int: pixel i of the window belongs to lane
+    i % 64, seven pixels at the most. By arithmetic no image gets past 7 x 4080^2 = 1.17e8 and 7 x 8160 x 4080 = 2.33e8; asserted all
+    the same on the worlds that come closest, from the arrays the restatement sums (a condition on the inputs, not on the device)."""
+    worst = [0]
+
+    def fn(v):
+        worst[0] = max(worst[0], int(np.abs(cases.lane_partials(v)).max()))
+        return int(v.sum())
+
+    for name, prev, cur in cases.saturated_worlds():
+        pts = cases.saturated_points(window)
+        with cases.observed_sums(fn):
+            f = K.flow(prev, cur, pts, window=window, levels=4)
+        assert cases.same_flow(f, K.flow(prev, cur, pts, window=window, levels=4)), name          # observing changes nothing
+    print("window", window, "largest lane partial", worst[0])
+    assert 0 < worst[0] < 2 ** 31 and worst[0] <= 7 * 8160 * 4080
+    assert np.array_equal(cases.lane_partials(np.arange(130).reshape(10, 13))[:3], [0 + 64 + 128, 1 + 65 + 129, 2 + 66])
+
+
+@pytest.mark.parametrize("window", SATURATED_WINDOWS)
+@pytest.mark.parametrize("levels", [1, 4])
+def test_saturated_worlds_host_function(host, window, levels):
+    for name, prev, cur in cases.saturated_worlds():
+        pts = cases.saturated_points(window)
+        f = K.flow(prev, cur, pts, window=window, levels=levels)
+        assert cases.same_flow(cases.host_flow(host, prev, cur, pts, window=window, levels=levels), f), name
+        assert f["status"][:7].all() or levels == 4, name
+        if levels == 1:          # K4 on level 0: the first and last admissible positions pass, the first outside fail
+            assert not f["status"][11:].any(), (name, f["status"].tolist())
+            tr = []
+            K.flow(prev, cur, pts[7:11], window=window, levels=1, trace=tr)
+            assert all(e["exit"] != "prev_outside" for e in tr), name
+
+
+@pytest.mark.parametrize("window", cases.SWEEP_WINDOWS)
+def test_window_sweep_host_function(host, window):
+    """Windows whose area fills a pass of 64 lanes (8, 16), starts a new one with one pixel (9, 17), and the other parities."""
+    levels = cases.deepest_levels(window)
+    assert levels == {5: 5, 7: 4, 8: 4, 9: 4, 11: 4, 12: 4, 15: 3, 16: 3, 17: 3, 20: 3}[window]
+    prev, cur = cases.shift_world("160x120", (3, -2))
+    pts = cases.border_points(160, 120)
+    f = K.flow(prev, cur, pts, window=window, levels=levels)
+    assert cases.same_flow(cases.host_flow(host, prev, cur, pts, window=window, levels=levels), f)
+    assert f["status"][:2].all() and not f["status"][3:6].any()
+
+
+def test_exit_world_takes_every_exit_on_a_coarse_level_and_on_level_0(host):
+    """From the trace, over the parameter sets: each of the six ways out of a level on a level above 0 and on level 0, K7's last look,
+    a current window that is outside before the first step and one that drifts out after one or more steps (each on a coarse
+    level and on level 0), a step that is exactly zero at an epsilon whose square is 0. No combination is missing."""
+    prev, cur, pts, g, sets = cases.exit_world()
+    seen, drift = set(), set()
+    for kw in sets:
+        tr = []
+        f = K.flow(prev, cur, pts, guesses=g, trace=tr, **kw)
+        assert cases.same_flow(cases.host_flow(host, prev, cur, pts, guesses=g, **kw), f), kw
+        here = {(e["exit"], e["level"] > 0) for e in tr}
+        print(kw, sorted(here))
+        seen |= here
+        drift |= {(min(e["steps"], 1), e["level"] > 0) for e in tr if e["exit"] == "cur_outside"}
+        cap = kw.get("iterations", 20)
+        assert all(e["steps"] <= cap for e in tr) and all(e["steps"] == cap for e in tr if e["exit"] == "cap")
+        if kw.get("eps") == cases.EPS_ZERO:
+            assert cases.EPS_ZERO ** 2 == 0.0 and cases.same_flow(K.flow(prev, cur, pts, guesses=g, **dict(kw, eps=0.0)), f)
+    assert seen == {(name, coarse) for name in cases.EXITS for coarse in (False, True)} | {("final_outside", False)}, sorted(seen)
+    assert drift == {(steps, coarse) for steps in (0, 1) for coarse in (False, True)}, sorted(drift)          # 1: one step or more
+    n = len(pts)
+    assert np.abs(g[n - 10:n - 6]).max() == 1e5          # the bound dsdtm_klt_flow admits
+
+
+def test_exit_world_oscillating_point_of_the_warp_world(host):
+    """The point test_mutant_no_halving_on_an_oscillating_point relies on, as the device test runs it."""
+    prev, cur, _ = cases.warp_world()
+    pts = KR.grid_points(160, 120)
+    tr = []
+    f = K.flow(prev, cur, pts, eps=cases.EPS_ZERO, trace=tr)
+    assert {(e["exit"], e["level"] > 0) for e in tr} >= {("oscillation", False), ("oscillation", True)}
+    assert cases.same_flow(cases.host_flow(host, prev, cur, pts, eps=cases.EPS_ZERO), f) and cases.same_flow(K.flow(prev, cur, pts, eps=0.0), f)
+
+
+def test_trace_is_opt_in_and_changes_nothing():
+    prev, cur, pts, g, sets = cases.exit_world()
+    tr = []
+    assert cases.same_flow(K.flow(prev, cur, pts, guesses=g), K.flow(prev, cur, pts, guesses=g, trace=tr))
+    assert len(tr) >= 4 * len(pts) and {e["point"] for e in tr} == set(range(len(pts)))
+    assert [e["level"] for e in tr if e["point"] == 0 and e["exit"] != "final_outside"] == [3, 2, 1, 0]
+
+
+def test_mixed_pairs_host_function(host):
+    pairs = cases.mixed_pairs()
+    assert [len(p["points"]) for p in pairs] == [1, 3, 2048, 4, 5, 64, 65]
+    assert sorted({p["window"] for p in pairs}) == [4, 9, 16, 21] and sorted({p["levels"] for p in pairs}) == [1, 2, 3, 4, 5]
+    for k, p in enumerate(pairs):
+        kw = {a: b for a, b in p.items() if a not in ("prev", "cur", "points")}
+        assert cases.same_flow(cases.host_flow(host, p["prev"], p["cur"], p["points"], **kw), cases.restated(p)), k
+
+
+@pytest.mark.parametrize("name", list(cases.COMPACTION))
+def test_compaction_worlds_are_what_they_claim(host, name):
+    rects, gw, gh, n_points, n_tracked = cases.COMPACTION[name]
+    prev, cur, gw, gh, r = cases.compaction_step(name)
+    s = r["status"]
+    print(name, r["n_tracked"], "".join(map(str, s.tolist())))
+    assert r["n_points"] == n_points == len(s) and r["n_tracked"] == int(s.sum())
+    if n_tracked is not None:
+        assert r["n_tracked"] == n_tracked
+        assert r["source"] == (KR.SOURCE_RANSAC if n_tracked >= 10 else KR.SOURCE_IDENTITY)
+    if "lanes 0 and 63" in name:
+        last = s[-64:]
+        assert last[0] == 1 and last[63] == 1 and 0 < last[1:63].sum() < 62
+    if "second round" in name:
+        assert 0 < s[:64].sum() < 64          # the first round is partly filled: `base` is neither 0 nor 64 when it is carried
+    if "second round full" in name:
+        assert s[64:].all()
+    if "second round empty" in name:
+        assert not s[64:].any()
+    if name == "64 points":
+        assert s.all()                        # one whole round, every lane a survivor
+    if r["n_tracked"]:
+        _same_step_host(host, prev, cur, r, KR.grid_points(160, 120, gw, gh), gw=gw, gh=gh)
+    else:
+        hs = cases.host_step(host, prev, cur, gw=gw, gh=gh)
+        assert hs["n_tracked"] == 0 and hs["n_points"] == n_points and not hs["status"].any()
+
+
+def test_mutant_totals_wrapped_to_32_bits_on_the_checker_world():
+    """A device that summed a window in 32 bits: told apart by the checker world at window 21, and by no world the suite had before."""
+    def wrapped(v):
+        return (int(v.sum()) + 2 ** 31) % 2 ** 32 - 2 ** 31
+
+    prev, cur = cases.checker_world()
+    pts = cases.saturated_points(21)
+    with cases.observed_sums(wrapped):
+        mut = K.flow(prev, cur, pts, window=21, levels=1)
+    base = K.flow(prev, cur, pts, window=21, levels=1)
+    assert not cases.same_flow(mut, base) and not np.array_equal(mut["status"], base["status"])
+    a, b = cases.shift_world("160x120", (3, -2))
+    with cases.observed_sums(wrapped):
+        mut = K.flow(a, b, cases.border_points(160, 120), window=21, levels=3)
+    assert cases.same_flow(mut, K.flow(a, b, cases.border_points(160, 120), window=21, levels=3))
+
+
+def test_mutant_more_than_ten_on_the_ten_survivor_world(monkeypatch):
+    """`n_tracked > 10` written for `>= 10`: told apart by the world with exactly ten survivors, and not by 8, 9 or 16."""
+    want = {name: cases.compaction_step(name)[4] for name in ("9 survivors", "10 survivors", "64 points")}
+    monkeypatch.setattr(KR, "MIN_TRACKED", 11)          # (>= 11 is > 10)
+    got = {name: cases.compaction_step(name)[4] for name in want}
+    assert want["10 survivors"]["source"] == KR.SOURCE_RANSAC and got["10 survivors"]["source"] == KR.SOURCE_IDENTITY
+    assert np.array_equal(got["10 survivors"]["H"], KR.IDENTITY) and not np.array_equal(want["10 survivors"]["H"], KR.IDENTITY)
+    for name in ("9 survivors", "64 points"):
+        assert got[name]["source"] == want[name]["source"] and np.array_equal(got[name]["H"], want[name]["H"])
+
+
 # ---- the surface --------------------------------------------------------------------------------------------------------------------
 
 def _exported(path):

@@ -172,6 +172,110 @@ def test_flow_five_levels_guesses_and_a_batch(ctx):
     assert cases.same_flow(got[1], K.flow(prev, cur, pts, guesses=g, levels=1)) and got[1]["status"].all()
 
 
+# ---- the edges tests/test_klt_cpu.py holds to their claims: saturated contrast, pass boundaries, every exit, the compaction ------------
+
+@pytest.mark.parametrize("levels", [1, 4])
+def test_flow_saturated_contrast(ctx, levels):
+    """Totals above 2^31 and right-hand sides beyond +-2^32 through wave_sum's two 32-bit halves; |dx| = 4080. One submission per level
+    count: four worlds x windows 21, 16, 10 and 4. At 160 x 120 the entry refuses four levels for windows 21 and 16 (the coarsest level,
+    20 x 15, cannot hold window + 3 pixels): that refusal is asserted, and those windows run at the three levels it accepts."""
+    def depth(window):
+        return min(levels, cases.deepest_levels(window))
+
+    assert [depth(w) for w in (21, 16, 10, 4)] == ([1, 1, 1, 1] if levels == 1 else [3, 3, 4, 4])
+    pairs = [dict(prev=prev, cur=cur, points=cases.saturated_points(window), window=window, levels=depth(window))
+             for _, prev, cur in cases.saturated_worlds() for window in (21, 16, 10, 4)]
+    got = ctx.flow(pairs)
+    for p, g in zip(pairs, got):
+        assert cases.same_flow(g, cases.restated(p)), (p["window"], p["levels"])
+    assert got[0]["status"][:7].all()
+    for p in pairs[:2]:
+        with pytest.raises(klt.KltError) as e:
+            ctx.flow([dict(p, levels=4)])
+        assert e.value.status == klt.ERR_INVALID and "coarsest" in e.value.message
+
+
+def test_flow_window_sweep_around_a_pass_of_64_lanes(ctx):
+    """Areas 64 and 256 fill a pass, 81 and 289 start the next with one pixel; as many levels as the entry accepts per window."""
+    prev, cur = cases.shift_world("160x120", (3, -2))
+    pts = cases.border_points(160, 120)
+    pairs = [dict(prev=prev, cur=cur, points=pts, window=w, levels=cases.deepest_levels(w)) for w in cases.SWEEP_WINDOWS]
+    for p, g in zip(pairs, ctx.flow(pairs)):
+        assert cases.same_flow(g, cases.restated(p)), p["window"]
+        assert g["status"][:2].all()
+
+
+def test_flow_exit_world(ctx):
+    """One call per parameter set. (The Python binding always passes a residual array, and dsdtm_klt_flow gives the kernel a device
+    residual whatever the caller wants: a run without one cannot be made from here and is left out.)"""
+    prev, cur, pts, g, sets = cases.exit_world()
+    for kw in sets:
+        pair = dict(prev=prev, cur=cur, points=pts, guesses=g, **kw)
+        got = ctx.flow([cases.device_pair(pair)])[0]
+        want = cases.restated(pair)
+        for f in ("iterations", "status"):
+            assert np.array_equal(got[f], want[f]), (kw, f, got[f].tolist(), want[f].tolist())
+        assert cases.same_flow(got, want), kw
+    a, b, _ = cases.warp_world()                                       # the oscillating point of test_mutant_no_halving_on_an_oscillating_point
+    pair = dict(prev=a, cur=b, points=KR.grid_points(160, 120), eps=cases.EPS_ZERO)
+    assert cases.same_flow(ctx.flow([cases.device_pair(pair)])[0], cases.restated(pair))
+
+
+def test_flow_mixed_submission(ctx):
+    """Unlike windows, level counts and point counts (1 to 2048) in one launch = the pairs one by one = the restatement."""
+    pairs = cases.mixed_pairs()
+    dev = [cases.device_pair(p) for p in pairs]
+    together = ctx.flow(dev)
+    for k, (p, d, g) in enumerate(zip(pairs, dev, together)):
+        assert len(g["status"]) == len(p["points"])
+        assert cases.same_flow(g, ctx.flow([d])[0]), k
+        assert cases.same_flow(g, cases.restated(p)), k
+
+
+def test_compaction_edges(ctx):
+    """klt_compact_kernel: 64, 65 and 128 points, rounds that are full, empty, or hold lanes 0 and 63 with holes between, and 9 / 10 / 0
+    survivors around `base >= min_tracked`; as one batch and as single calls. After the step with no survivor the model goes on."""
+    names = list(cases.COMPACTION)
+    worlds = [cases.compaction_step(name) for name in names]
+
+    def run(batched):
+        models = [klt.KltModel(ctx, 160, 120) for _ in names]
+        seeds = [dict(model=m, image=w[0], grid_w=w[2], grid_h=w[3]) for m, w in zip(models, worlds)]
+        steps = [dict(model=m, image=w[1], grid_w=w[2], grid_h=w[3]) for m, w in zip(models, worlds)]
+        if batched:
+            ctx.steps(seeds)
+            out = ctx.steps(steps)
+        else:
+            for s in seeds:
+                ctx.steps([s])
+            out = [ctx.steps([s])[0] for s in steps]
+        return models, out
+
+    for batched in (True, False):
+        models, out = run(batched)
+        for name, w, got in zip(names, worlds, out):
+            _same_step(got, w[4], (name, batched))
+            assert got["n_points"] == cases.COMPACTION[name][3]
+        by = dict(zip(names, out))
+        assert by["9 survivors"]["source"] == klt.SOURCE_IDENTITY and by["9 survivors"]["n_tracked"] == 9
+        assert by["0 survivors"]["source"] == klt.SOURCE_IDENTITY and by["0 survivors"]["n_tracked"] == 0
+        assert by["10 survivors"]["n_tracked"] == 10 and by["10 survivors"]["source"] == worlds[names.index("10 survivors")][4]["source"] == klt.SOURCE_RANSAC
+        if batched:          # the chain after no survivor at all: the next step on a textured frame
+            k = names.index("0 survivors")
+            a, b = cases.painted_world([])
+            r = KR.KltModel(160, 120, gw=17, gh=13)
+            for img in worlds[k][:2]:
+                r.step(img)
+            want = r.step(b)
+            _same_step(models[k].step(b, grid_w=17, grid_h=13), want, "after 0 survivors")
+            assert want["n_tracked"] == 0          # (tracked from the flat frame: nothing again)
+            want = r.step(a)
+            _same_step(models[k].step(a, grid_w=17, grid_h=13), want, "a textured pair after 0 survivors")
+            assert want["source"] == KR.SOURCE_RANSAC and want["n_tracked"] > 10
+        for m in models:
+            m.close()
+
+
 def test_refusals_leave_every_output_and_model_untouched(ctx):
     prev, cur = cases.shift_world("160x120", (3, -2))
     m = klt.KltModel(ctx, 160, 120)
