@@ -96,6 +96,12 @@ MORE_ADDONS = {
             ["klt.h", "homography.h", "kernels.h", "addon_host.h", "exports.map", os.path.join(_INC, "dsdtm_amd_klt.h"),
              os.path.join(_INC, "dsdtm_amd_homography.h"), os.path.join(_INC, "dsdtm_amd.h")],
             os.path.join(HERE, "libdsdtm_amd_klt.so")),
+    # include/dsdtm_amd_framediff.h: Moving_Detecter::Mod_FrameDiff — warp, difference, threshold, open, dilate and the feature test
+    # (F1, the inverse of H, is the host header's function: one definition for the library and the host path)
+    "framediff": (["framediff_api.cpp", "framediff.hip"],
+                  ["framediff.h", "addon_host.h", "exports.map", os.path.join("..", "host", "dsdtm_framediff_host.hpp"),
+                   os.path.join(_INC, "dsdtm_amd_framediff.h"), os.path.join(_INC, "dsdtm_amd.h")],
+                  os.path.join(HERE, "libdsdtm_amd_framediff.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")

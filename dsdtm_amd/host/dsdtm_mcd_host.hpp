@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/dsdtm_amd_mcd.h"
+#include "dsdtm_framediff_host.hpp"
 #include "dsdtm_motion_host.hpp"
 
 namespace DSDTM {
@@ -87,6 +88,53 @@ inline BoxResult mcd_box_host(const uint8_t* mask, int w, int h, int stride, uin
     return out;
 }
 
+// What MotionDetector::Mod_FrameDiff runs on: rules F1-F8 of include/dsdtm_amd_framediff.h for one pair, on the device
+// (dsdtm_framediff_step, libdsdtm_amd_framediff.so: link it when on_device is used) or with frame_diff_host; the same bytes either way.
+// A class of its own, made by the caller, so that a program that never calls Mod_FrameDiff links what it linked before.
+// on_device defaults to true: the device wins everywhere measured, the issue's candidate included (profiles/r25_framediff.txt, 640x480, ONE pair
+// from pageable memory with the mask read back: 116 us against 4821 us for frame_diff_host on one thread, this repository's C++, not OpenCV).
+#ifndef FRAMEDIFF_ON_DEVICE_DEFAULT
+#define FRAMEDIFF_ON_DEVICE_DEFAULT true
+#endif
+class FrameDiffer {
+public:
+    explicit FrameDiffer(int device = 0, bool on_device = FRAMEDIFF_ON_DEVICE_DEFAULT) : on_device_(on_device) {
+        if (on_device_ && dsdtm_framediff_create(device, &ctx_) != DSDTM_OK)
+            throw std::runtime_error(std::string("dsdtm_framediff_create: ") + dsdtm_framediff_last_error(nullptr));
+    }
+    ~FrameDiffer() { if (ctx_) dsdtm_framediff_destroy(ctx_); }
+    FrameDiffer(const FrameDiffer&) = delete;
+    FrameDiffer& operator=(const FrameDiffer&) = delete;
+    // mask: width x height bytes, packed. Throws where the entry refuses.
+    dsdtm_framediff_result run(const uint8_t* a, int a_stride, const uint8_t* b, int b_stride, int width, int height, const double H[9], int flags,
+                               int threshold, int maxval, uint8_t* mask, int n_features, const float* feature_px, uint8_t* feature_on_mask) {
+        dsdtm_framediff_result r{};
+        if (on_device_) {
+            dsdtm_framediff_desc d{};
+            d.a = a; d.b = b; d.width = width; d.height = height; d.a_stride = a_stride; d.b_stride = b_stride;
+            std::memcpy(d.H, H, sizeof d.H);
+            d.flags = flags; d.threshold = threshold; d.maxval = maxval; d.mask = mask; d.mask_stride = width;
+            d.n_features = n_features; d.feature_px = feature_px; d.feature_on_mask = feature_on_mask;
+            if (dsdtm_framediff_step(ctx_, &d, &r) != DSDTM_OK) throw std::runtime_error(std::string("dsdtm_framediff_step: ") + dsdtm_framediff_last_error(ctx_));
+            return r;
+        }
+        for (int i = 0; i < n_features; ++i) {          // (the entry's refusal; frame_diff_host takes the features on trust)
+            const float x = std::nearbyintf(feature_px[2 * (size_t)i]), y = std::nearbyintf(feature_px[2 * (size_t)i + 1]);
+            if (!(x >= 0 && x < (float)width && y >= 0 && y < (float)height)) throw std::runtime_error("frame_diff_host: a feature rounds outside the image");
+        }
+        const FrameDiffHost h = frame_diff_host(a, a_stride, b, b_stride, width, height, H, flags, threshold, maxval, mask, width, n_features, feature_px, feature_on_mask);
+        if (!h.ok) throw std::runtime_error("frame_diff_host: H is singular or not finite");
+        std::memcpy(r.M, h.M, sizeof r.M);
+        r.n_foreground = h.n_foreground; r.n_flagged = h.n_flagged;
+        return r;
+    }
+    bool on_device() const { return on_device_; }
+
+private:
+    dsdtm_framediff_ctx* ctx_ = nullptr;
+    bool on_device_ = true;
+};
+
 // Moving_Detecter (src/Moving_Detection.cpp) + Frame::Motion_Removal (src/Frame.cpp:342-363) with Mod_FastMCD = the WHOLE
 // MCDWrapper::Run. Two paths, the same bytes; link both libraries (each path creates the context of its own library only):
 //   host_box = true, the default and for ONE tracker the faster path (profiles/r23_mcd.txt: 346 us against 1039 us at 640x480):
@@ -140,6 +188,24 @@ public:
         klt.GetHomography(H);
         return Mod_FastMCD(gray, width, height, stride, (const double*)H, features, out);
     }
+    // Moving_Detecter::Mod_FrameDiff (src/Moving_Detection.cpp:36-63) behind its findHomography: H is the caller's (a HomographyEstimator's
+    // fit of frame B's points onto frame A's, or a KLTWrapper's with DSDTM_FRAMEDIFF_INVERSE_MAP in `flags`), `differ` a FrameDiffer the
+    // caller owns. gray_b IS FRAME B: the reference's :45 passes frame A twice (QUIRK 1 of include/dsdtm_amd_framediff.h); a caller who
+    // wants that passes gray_a for both. maxval 0 is the reference's 200, at which Motion_Removal removes nothing (QUIRK 2); 255 makes
+    // the mask act. Returns false — nothing done — with fewer than 4 points (:40-41).
+    template <class Differ>
+    bool Mod_FrameDiff(Differ& differ, const uint8_t* gray_a, const uint8_t* gray_b, int width, int height, int stride, size_t n_points, const double H[9],
+                       const std::vector<Feature2f>& features, Mask* out, int flags = 0, int threshold = DSDTM_FRAMEDIFF_THRESHOLD, int maxval = 0) {
+        if (n_points < 4) return false;
+        Mask m;
+        m.width = width; m.height = height; m.data.assign((size_t)width * (size_t)height, 0);
+        on_mask_.assign(features.size(), 0);
+        last_framediff_ = differ.run(gray_a, stride, gray_b, stride, width, height, H, flags, threshold, maxval, m.data.data(), (int)features.size(),
+                                     features.empty() ? nullptr : &features[0].x, features.empty() ? nullptr : on_mask_.data());
+        if (out) *out = std::move(m);
+        return true;
+    }
+    const dsdtm_framediff_result& framediff() const { return last_framediff_; }
     std::vector<Feature2f> Motion_Removal(const std::vector<Feature2f>& features, bool faithful = true) const {
         if (features.size() != on_mask_.size()) throw std::runtime_error("Motion_Removal: not the features the last Mod_FastMCD was given");
         std::vector<Feature2f> out;
@@ -165,6 +231,7 @@ private:
     int required_rows_ = 0;
     bool host_box_ = true;
     BoxResult last_;
+    dsdtm_framediff_result last_framediff_{};
     std::vector<uint8_t> on_mask_;
 };
 

@@ -231,6 +231,47 @@ class MotionDetector:
         self.klt.RunTrack(image)
         return self.Run(image, self.klt.GetHomography().reshape(9), features=features, want_raw=want_raw)
 
+    def _framediff(self, a, b, H, flags, features, threshold, maxval):
+        if getattr(self, "framediff", None) is None:
+            from . import framediff as _fd
+            self.framediff = _fd.FrameDiffContext(self.ctx.device)
+        r = self.framediff.step(a, b, H, flags=flags, threshold=threshold, maxval=maxval, features=features)
+        self.mask, self.last_framediff = r["mask"], r
+        self._pending = r["flags"]
+        return self.mask
+
+    def Mod_FrameDiff(self, image_a, image_b, points_a, points_b, features=None, threshold=50, maxval=0):
+        """Moving_Detecter::Mod_FrameDiff (src/Moving_Detection.cpp:36-63) over libdsdtm_amd_homography.so and libdsdtm_amd_framediff.so
+        (contexts made on first use, on this detector's device): H = dsdtm_find_homography(points_b, points_a), image_b warped by it,
+        image_a - warped, threshold, open, dilate. Fewer than 4 points: None (:40-41); so is a fit that finds nothing.
+        image_b IS FRAME B: the reference's :45 passes frame A twice (QUIRK 1 of the header); a caller who wants that passes image_a for
+        both. maxval 0 is the reference's 200, at which motion_removal removes nothing (QUIRK 2); 255 makes the mask act."""
+        pa, pb = np.asarray(points_a, np.float32).reshape(-1, 2), np.asarray(points_b, np.float32).reshape(-1, 2)
+        if len(pa) < 4:
+            return None
+        if getattr(self, "homography", None) is None:
+            from . import homography as _h
+            self.homography = _h.HomographyContext(self.ctx.device)
+        fit = self.homography.find_homography(pb, pa)
+        if fit["found"] != 1:
+            return None
+        return self._framediff(image_a, image_b, fit["H"], 0, features, threshold, maxval)
+
+    def Mod_FrameDiff_KLT(self, image, features=None, threshold=50, maxval=0):
+        """Mod_FrameDiff from images alone: a KLTWrapper (dsdtm_amd/klt.py; made on first use) tracks its grid from the last image into
+        this one; its H maps the current frame to the last one, which is the map's own direction, so it goes in with INVERSE_MAP, a the
+        current image and b the previous one. The first image seeds the tracker and returns None."""
+        if getattr(self, "klt", None) is None:
+            from . import klt as _klt
+            self.klt = _klt.KLTWrapper(device=self.ctx.device)
+        prev = getattr(self, "_framediff_prev", None)
+        self.klt.RunTrack(image)
+        self._framediff_prev = image.clone() if hasattr(image, "clone") else np.array(image, np.uint8)      # a copy: the caller may refill its buffer
+        if prev is None:
+            return None
+        from . import framediff as _fd
+        return self._framediff(image, prev, self.klt.GetHomography().reshape(9), _fd.INVERSE_MAP, features, threshold, maxval)
+
     def motion_removal(self, features):
         """Frame::Motion_Removal against the last image Run returned: (keep, rebuilt), as dsdtm_amd.motion.MovingDetector.motion_removal."""
         f = np.asarray(features, np.float32).reshape(-1, 2)
