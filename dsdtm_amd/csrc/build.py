@@ -102,6 +102,12 @@ MORE_ADDONS = {
                   ["framediff.h", "addon_host.h", "exports.map", os.path.join("..", "host", "dsdtm_framediff_host.hpp"),
                    os.path.join(_INC, "dsdtm_amd_framediff.h"), os.path.join(_INC, "dsdtm_amd.h")],
                   os.path.join(HERE, "libdsdtm_amd_framediff.so")),
+    # include/dsdtm_amd_rarsac.h: Rarsac_base::RejectFundamental — the grid-guided RANSAC for the fundamental matrix, lane = hypothesis
+    # (R1, the bin of a point, is the host header's function: one definition for the library and the host path)
+    "rarsac": (["rarsac_api.cpp", "rarsac.hip"],
+               ["rarsac.h", "addon_host.h", "exports.map", os.path.join("..", "host", "dsdtm_rarsac_host.hpp"),
+                os.path.join(_INC, "dsdtm_amd_rarsac.h"), os.path.join(_INC, "dsdtm_amd.h")],
+               os.path.join(HERE, "libdsdtm_amd_rarsac.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")
