@@ -108,6 +108,12 @@ MORE_ADDONS = {
                ["rarsac.h", "addon_host.h", "exports.map", os.path.join("..", "host", "dsdtm_rarsac_host.hpp"),
                 os.path.join(_INC, "dsdtm_amd_rarsac.h"), os.path.join(_INC, "dsdtm_amd.h")],
                os.path.join(HERE, "libdsdtm_amd_rarsac.so")),
+    # include/dsdtm_amd_clahe.h: cv::CLAHE(3.0, 8x8) of the reference's drivers — per-tile tables, then the interpolation
+    # (E1 and E2, the geometry of a frame, are the host header's function: one definition for the library and the host path)
+    "clahe": (["clahe_api.cpp", "clahe.hip"],
+              ["clahe.h", "addon_host.h", "exports.map", os.path.join("..", "host", "dsdtm_clahe_host.hpp"),
+               os.path.join(_INC, "dsdtm_amd_clahe.h"), os.path.join(_INC, "dsdtm_amd.h")],
+              os.path.join(HERE, "libdsdtm_amd_clahe.so")),
 }
 OUT = os.path.join(HERE, "libdsdtm_amd.so")
 OUT_DIAG = os.path.join(HERE, "libdsdtm_amd_diag.so")

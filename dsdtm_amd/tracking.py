@@ -313,6 +313,28 @@ class Tracker:
             self._prefetched.pop(0)[1].close()
         return df, gray_t, depth_t
 
+    def prefetch_equalized(self, image, depth=None, depth_scale: float = 5000.0):
+        """prefetch() behind cv::createCLAHE(3.0, cv::Size(8, 8))->apply, what the reference's drivers do to every image before the
+        detector (Test/test_Feature_detection.cpp:85-86): dsdtm_clahe_apply into a torch device tensor, then the existing prefetch on
+        its data_ptr(). `image` (uint8): a 2-D numpy array or torch tensor; `depth` goes to prefetch() as it is. TrackFrame(image, ...)
+        with the same image object starts at Run on the equalised frame. The Frame object keeps the caller's image; the equalised one
+        is the returned tensor. Returns (capi.DeviceFrame, equalised gray); the tensor stays alive with the frame."""
+        import torch
+        from . import clahe
+        if getattr(self, "_clahe_ctx", None) is None:
+            self._clahe_ctx = clahe.ClaheContext(self.ctx.device if hasattr(self.ctx, "device") else 0)
+        dev = torch.device("cuda", self._clahe_ctx.device)
+        gray_t = torch.empty(tuple(image.shape), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)              # (the tensor exists; the add-on's stream is its own)
+        self._clahe_ctx.apply(image, gray_t)
+        h, w = gray_t.shape
+        df = capi.DeviceFrame.prefetch(self.ctx, (gray_t.data_ptr(), w, h, gray_t.stride(0)), self.levels, depth, depth_scale)
+        df._keep = list(df._keep) + [gray_t]
+        self._prefetched.append((image, df))
+        while len(self._prefetched) > 2:
+            self._prefetched.pop(0)[1].close()
+        return df, gray_t
+
     def UndistortFeatures(self, frame):
         """Frame::UndistortFeatures (src/Frame.cpp:94-150) on `frame`: the pixel of every feature that is not mbInitial goes through
         cv::undistortPoints(.., K, D, noArray(), K) (rule U5 of include/dsdtm_amd_undistort.h) and its bearing is recomputed, through
